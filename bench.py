@@ -7,11 +7,18 @@ pretrained checkpoint offline).  One step = zero_grad + forward + fused
 upsample/cross-entropy loss + backward (+ RCCL gradient all-reduce when N > 1)
 + torch.optim.Adam(lr=1.5e-4) step -- the reference loop of src/train.py:35-39.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 N > 1 runs under torch.distributed.run (one process per GPU, RCCL), per-GPU
 batch fixed (weak scaling); value = all images / max-over-ranks time.
 
-Also reported:
+A plain run does only what the headline needs: set up, W warm-up steps, K timed steps,
+the result line (step_roofline is arithmetic on the headline, no run of its own).
+--dump-outputs DIR writes what the last timed step handed its caller (loss, parameter
+gradients, updated parameters and buffers) as DIR/<name>.npy, float32, at most 64 MB
+(a fixed seeded sample of the elements when the whole is larger); inputs and initial
+weights are seeded, so two builds can be compared output for output.
+
+With --full, also reported (the --no-* switches take single blocks out again):
   roofline      -- the dense 3x3 conv family (forward + data gradient), timed with
                    HIP events around those launches inside the timed region:
                    achieved = their algorithmic FLOPs (f32, vs the f32 MFMA peak) or
@@ -59,6 +66,15 @@ def parse():
     ap.add_argument("--height", type=int, default=256)
     ap.add_argument("--width", type=int, default=512)
     ap.add_argument("--classes", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: the per-launch roofline timing and its untimed "
+                         "passes, the CPU baseline, and on the default line the nested bf16io / unet_cfg5 / "
+                         "world-1 DataParallel / infer blocks (off by default; the --no-* switches below take "
+                         "single parts out of a --full run)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (train: loss, gradients, "
+                         "updated parameters and buffers; infer: class mask and logits) as DIR/<name>.npy, float32, "
+                         "at most 64 MB in all (a fixed seeded sample of the elements beyond that)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--no-timer", action="store_true", help="skip the per-launch HIP-event roofline timing")
@@ -89,6 +105,29 @@ def parse():
     ap.add_argument("--model", choices=("MobileNetV2UNet", "UNet"), default="MobileNetV2UNet",
                     help="UNet = BASELINE configs[4] shape family (use --height 512 --width 1024 --batch 8)")
     return ap.parse_args()
+
+
+DUMP_BUDGET_BYTES = 60 * 1000 * 1000  # --dump-outputs: float32 payload of all files together (limit: 64 MB)
+
+
+def dump_outputs(path: str, arrays) -> None:
+    """Write {name: tensor} as path/<name>.npy in float32.  When everything together exceeds
+    DUMP_BUDGET_BYTES, every array keeps the same fraction of its elements (at least 1024): a
+    sorted index sample drawn by a generator seeded with the array's position, so the same
+    arguments select the same elements in every run and every build."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    total = 4 * sum(t.numel() for t in arrays.values())
+    frac = min(1.0, DUMP_BUDGET_BYTES / max(total, 1))
+    for i, (name, t) in enumerate(arrays.items()):
+        a = t.detach().to("cpu", torch.float32).contiguous().numpy().reshape(-1)
+        keep = max(int(a.size * frac), 1024)
+        if frac < 1.0 and keep < a.size:
+            idx = np.sort(np.random.Generator(np.random.PCG64(i)).choice(a.size, size=keep, replace=False))
+            a = a[idx]
+        else:
+            a = a.reshape(tuple(t.shape) or (1,))
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def cpu_model() -> str:
@@ -131,11 +170,12 @@ def cpu_baseline(args):
                       f"{steps} timed steps ({dt:.1f} s) after 1 warm-up, torch CPU fp32"}
 
 
-def infer_measure(args, math, frames, cpu_baseline=True):
+def infer_measure(args, math, frames, cpu_baseline=True, modes=("graph", "eager", "graph_h2d"), dump=None):
     """configs[3]: inference.py's per-frame path (preprocess_image -> model.eval() forward ->
     argmax + INTER_NEAREST mask) for a 720x1280 uint8 BGR frame resized to 128x256, bs=1,
     replayed as one HIP graph.  Returns per-frame latencies (graph / eager / graph with the
-    H2D frame copy) and the CPU path's frames/s."""
+    H2D frame copy; `modes` selects them, "graph" is the headline) and the CPU path's frames/s.
+    dump: directory for the graph mode's last mask and logits (--dump-outputs)."""
     import numpy as np
     from seg_amd import MobileNetV2UNet, deterministic_init
     from seg_amd.infer import Predictor
@@ -144,7 +184,7 @@ def infer_measure(args, math, frames, cpu_baseline=True):
     g = np.random.Generator(np.random.PCG64(0))
     frame = g.integers(0, 256, (720, 1280, 3), dtype=np.uint8)
     res = {}
-    for mode in ("graph", "eager", "graph_h2d"):
+    for mode in modes:
         pred = Predictor(model, frame_hw=(720, 1280), graph=mode != "eager", math=math)
         pred.set_frame(frame)
         fn = (lambda: pred(frame)) if mode == "graph_h2d" else pred.step
@@ -157,6 +197,8 @@ def infer_measure(args, math, frames, cpu_baseline=True):
             fn()
         torch.cuda.synchronize()
         res[mode] = (time.perf_counter() - t0) / n
+        if dump and mode == "graph":
+            dump_outputs(dump, {"mask": pred.mask, "logits": pred.logits()})
     cpu = None
     if cpu_baseline:
         from oracle import cvresize, segref
@@ -179,8 +221,8 @@ def infer_measure(args, math, frames, cpu_baseline=True):
                "sample": f"oracle cvresize.preprocess_image + segref eval forward (torch CPU fp32) + class_mask, "
                          f"{k} frames in {dt:.1f} s"}
     return {"value": round(1.0 / res["graph"], 1), "unit": "frames/s", "ms_per_frame": round(res["graph"] * 1e3, 4),
-            "latency_ms": {"graph": round(res["graph"] * 1e3, 4), "eager": round(res["eager"] * 1e3, 4),
-                           "graph_with_h2d_frame_copy": round(res["graph_h2d"] * 1e3, 4)},
+            "latency_ms": {{"graph_h2d": "graph_with_h2d_frame_copy"}.get(m, m): round(res[m] * 1e3, 4)
+                           for m in modes},
             "frames": frames, "cpu_baseline": cpu}
 
 
@@ -194,7 +236,10 @@ INFER_WORKLOAD = ("inference.py per-frame path: cv2-style resize + normalise, BN
 def bench_infer(args):
     """configs[3] as the headline (--workload infer).  value = frames/s with the frame already in HBM."""
     torch.cuda.set_device(0)
-    r = infer_measure(args, args.math, args.frames, not args.no_cpu_baseline)
+    # a plain run times the headline (the graph replay) alone; the eager and H2D latencies and
+    # the CPU baseline are --full's
+    r = infer_measure(args, args.math, args.frames, args.full and not args.no_cpu_baseline,
+                      modes=("graph", "eager", "graph_h2d") if args.full else ("graph",), dump=args.dump_outputs)
     line = {"metric": "frames/sec inference MobileNetV2UNet 720x1280 frame -> 128x256, bs=1 (BASELINE configs[3])",
             "value": r["value"], "unit": "frames/s", "n_gpus": 1, "steps": args.frames,
             "warmup": args.warmup, "ms_per_step": r["ms_per_frame"], "higher_is_better": True,
@@ -229,6 +274,8 @@ def check_world(world: int, gpus: int):
 
 def main():
     args = parse()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be at least 1 and --warmup at least 0")
     if args.math is None:
         args.math = "f16" if args.workload == "infer" else "f32"
     if args.workload == "infer" and args.math == "bf16io":
@@ -261,9 +308,10 @@ def main():
             torch.distributed.init_process_group(args.dist_backend)
         assert torch.distributed.get_world_size() == args.gpus
 
-    head = train_workload(args, args.math, dev, world, rank, dist)
+    head = train_workload(args, args.math, dev, world, rank, dist, dump=args.dump_outputs if rank == 0 else None)
     nested = None
-    default_line = args.math == "f32" and args.model == "MobileNetV2UNet"
+    # everything below the headline is --full's: a plain run prints the headline alone
+    default_line = args.full and args.math == "f32" and args.model == "MobileNetV2UNet"
     if default_line and not args.no_bf16io_block:
         # BASELINE configs[2]'s arithmetic on the same workload (the north-star HBM target):
         # its own model, warm-up and timed region after the headline's
@@ -292,7 +340,7 @@ def main():
         dp1 = {m: dp_world1(args, m, dev) for m in ("f32", "bf16io")}
     if rank == 0:
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cpu = cpu_baseline(args)
         line = {"metric": f"images/sec fwd+bwd {args.model} {args.height}x{args.width} bs={args.batch}/GPU",
                 "value": head["value"], "unit": "images/s", "n_gpus": world, "steps": args.steps,
@@ -321,7 +369,7 @@ def main():
                                  "scaling": "weak", **unet}
         if dp1 is not None:
             line["multi_gpu"] = {"world1_rccl": dp1}
-        if world == 1 and args.model == "MobileNetV2UNet" and not args.no_infer_block:
+        if args.full and world == 1 and args.model == "MobileNetV2UNet" and not args.no_infer_block:
             # BASELINE configs[3] on the same GPU after the training lines (its own timed loop)
             r = infer_measure(args, "f16", 500, cpu_baseline=False)
             line["infer"] = {"workload": f"BASELINE configs[3]: {INFER_WORKLOAD}", "dtype": "f16",
@@ -414,11 +462,12 @@ def _cfg_name(args, math):
     return f"BASELINE configs[4] shape, {math} conv math"
 
 
-def train_workload(args, math, dev, world, rank, dist):
+def train_workload(args, math, dev, world, rank, dist, dump=None):
     """Warm up, then time args.steps training steps of args.model with conv math `math`
-    (barrier + synchronize on both sides, max over ranks), then the untimed roofline
-    passes.  Returns value / ms_per_step / final_loss / roofline / step_roofline /
-    multi_gpu; frees the model's plans afterwards."""
+    (barrier + synchronize on both sides, max over ranks), then, with --full, the untimed
+    roofline passes.  Returns value / ms_per_step / final_loss / roofline / step_roofline /
+    multi_gpu; frees the model's plans afterwards.  dump: directory for the last timed
+    step's outputs (--dump-outputs), written before anything else steps the model."""
     import seg_amd
     from seg_amd import deterministic_init, synthetic_batch
     from seg_amd import engine
@@ -449,7 +498,7 @@ def train_workload(args, math, dev, world, rank, dist):
     # live per-launch HIP events on the roofline family only (each event pair is a marker
     # packet on the queue: timing all ~130 conv launches costs ~3 % of the step)
     conv3 = {"igemm3_fwd", "igemm3_dgrad", "wino3_fwd", "wino3_dgrad"}
-    timer = None if args.no_timer else engine.KernelTimer(kinds=conv3)
+    timer = engine.KernelTimer(kinds=conv3) if args.full and not args.no_timer else None
     if dist:
         torch.distributed.barrier()
     torch.cuda.synchronize()
@@ -463,6 +512,14 @@ def train_workload(args, math, dev, world, rank, dist):
     dt = time.perf_counter() - t0
     engine.TIMER = None
     final_loss = loss.item()
+    if dump:
+        out = {"loss": loss}
+        for k, p in core.named_parameters():
+            if p.grad is not None:
+                out["grad." + k] = p.grad
+        out.update(("param." + k, p) for k, p in core.named_parameters())
+        out.update(("buffer." + k, b) for k, b in core.named_buffers())
+        dump_outputs(dump, out)
     per_rank = [dt]
     if dist:
         t = torch.zeros(world, device=dev, dtype=torch.float64)
@@ -473,7 +530,7 @@ def train_workload(args, math, dev, world, rank, dist):
     images = args.batch * args.steps * world
     value = images / dt
     scaling = None
-    if dist:
+    if dist and args.full:
         # same-run reference for the weak-scaling efficiency: the same K steps on every rank
         # with no communication at all (DataParallel.no_sync: no gradient all-reduce; the BN
         # buffer broadcast switched off too), max over ranks.  One untimed step first: the

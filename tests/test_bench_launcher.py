@@ -37,6 +37,35 @@ def test_rank_refuses_mismatch_before_touching_the_gpu():
     assert "WORLD_SIZE=2 but --gpus 1" in r.stderr
 
 
+def test_plain_run_is_the_default_and_full_is_an_option(monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "out"
+
+
+def test_dump_outputs_float32_whole_or_fixed_sample(tmp_path, monkeypatch):
+    import numpy as np
+    import torch
+    arrays = {"a": torch.arange(10000, dtype=torch.float64).reshape(100, 100), "s": torch.tensor(3.5),
+              "h": torch.ones(8, dtype=torch.float16)}
+    bench.dump_outputs(str(tmp_path / "whole"), arrays)
+    got = {n: np.load(tmp_path / "whole" / (n + ".npy")) for n in arrays}
+    assert all(v.dtype == np.float32 for v in got.values())
+    assert got["a"].shape == (100, 100) and got["s"].shape == (1,) and got["h"].shape == (8,)
+    assert np.array_equal(got["a"], arrays["a"].numpy()) and got["s"][0] == 3.5
+    # over the budget: every large array keeps the same fraction, the same elements in every run
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 4 * 5000)
+    bench.dump_outputs(str(tmp_path / "s1"), arrays)
+    bench.dump_outputs(str(tmp_path / "s2"), arrays)
+    a1, a2 = np.load(tmp_path / "s1" / "a.npy"), np.load(tmp_path / "s2" / "a.npy")
+    assert np.array_equal(a1, a2) and a1.dtype == np.float32
+    assert 4000 <= a1.size <= 5000 and np.all(np.diff(a1) > 0) and a1.min() >= 0 and a1.max() < 10000
+    assert np.load(tmp_path / "s1" / "h.npy").shape == (8,)
+
+
 def test_parent_forwards_child_exit_code(monkeypatch):
     seen = {}
 

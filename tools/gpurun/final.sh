@@ -11,6 +11,6 @@ for m in f32 bf16io; do
   bash tools/gpurun/roof.sh ${tag}_$m --math $m || exit 1
   python tools/queues.py gpurun_out/${tag}_$m/prof/run_kernel_trace.csv > gpurun_out/${tag}_$m/queues.txt || exit 1
 done
-timeout -k 10 400 python bench.py > $d/bench.json 2> $d/bench.err || { tail -5 $d/bench.err; exit 1; }
+timeout -k 10 400 python bench.py --full > $d/bench.json 2> $d/bench.err || { tail -5 $d/bench.err; exit 1; }
 bash tools/gpurun/unet_cfg5.sh ${tag}_unet || exit 1
 tail -c 400 $d/bench.json
