@@ -18,12 +18,25 @@ Gradients of a buffer region are written by the first consumer in reverse
 order and accumulated by later ones; a residual (InvertedResidual
 `x + conv(x)`) hands its upstream gradient to the first writer of dx as a
 fused addend.
+
+Routes: which kernel runs a conv is decided once per program and direction, in one
+place.  pick_routes() gives every ConvOp a Route for its forward, data gradient and
+weight gradient (op.route_f / route_d / route_w): the kernel family, the resolved C
+entry point, the roofline timer kind, the BN-statistics tile geometry, the workspace,
+the split count and the packed weight it reads.  The picker is a pure function of the
+shapes, the conv math, the engine switches below and the library's host-side queries
+(no tensor, no device call; tests/test_engine_routes.py runs it without a GPU).
+Program._build_pack allocates the packed weights the routes name, and the walk only
+reads routes: ConvOp._launch holds the one argument list per family that the forward
+and the data gradient share.  A new kernel is wired in by adding its case to the
+picker and, if its argument list is new, to _launch.
 """
 from __future__ import annotations
 
 import contextlib
 import ctypes
 import os
+from typing import NamedTuple
 
 import torch
 from torch import nn
@@ -57,6 +70,25 @@ _ROW_TILES = {}  # (M, Cout) -> (row tiles, tile height) of seg_conv_igemm
 
 
 _IG2 = {}  # (M, Cout, Cin, ks) -> (tile rows, row tiles, splits, workspace floats) or None
+_TILE_GEN = 0  # bumped by force_tiles; part of Program.pack's key, so the next walk picks every route again
+
+
+class Route(NamedTuple):
+    """How one direction of one conv runs (pick_routes); immutable, holds no tensor."""
+    family: str                  # pw | halo | wino | wino_fused | igemm2 | igemm | dw; weight gradients: dw | wino |
+                                 # wino16 | wgrad2 | igemm
+    name: str                    # C entry point, storage / math / weight-format suffixes applied
+    timer: str | None            # roofline timer kind (bench.py selects on these); None: an untimed launch
+    mode: int | None = None      # packed weight it reads: seg_pack_job layout (0 forward, 1 data gradient, 2 depthwise,
+                                 # 3 / 4 their Winograd U; | 16 = bf16), None = no pack of its own (a 1x1 conv's
+                                 # weight as it is; the depthwise data gradient reads the forward's)
+    ldk: int = 0                 # ... and its row stride
+    tiles: tuple | None = None   # forward into a BatchNorm: (row tiles, rows per tile) of the statistics partials
+    work: int = 0                # workspace floats
+    zero: bool = False           # ... zero-filled before the launch
+    splits: int = 0              # weight gradient: split-K slabs / blocks of partials the reduce sums
+    bnout: str | None = None     # implicit-GEMM data gradient: its entry point that also emits BN-backward partials
+    fallback: "Route | None" = None  # data gradient: the route when the addend is not 16-byte aligned at walk time
 
 
 def _pw_pick(op, v: int):
@@ -88,9 +120,12 @@ def igemm2_plan(M: int, cout: int, cin: int, ks: int):
 
 def force_tiles(igemm: int | None = None, igemm2: int | None = None) -> None:
     """Tuning hook: force the implicit GEMM's (seg_igemm_force_tile) and / or igemm2's (seg_igemm2_force_tile) tile
-    table entry (-1 = the cost model again), and drop every memoised tile-dependent plan (row tiles, igemm2 plans) so
-    the next program walk sizes its workspaces for the tile actually launched.  Plans recorded before the
-    change keep their tapes: release_plans() / a fresh Predictor re-record them."""
+    table entry (-1 = the cost model again), and drop every memoised tile-dependent plan (row tiles, igemm2 plans) and
+    every program's routes, so the next program walk picks and sizes its workspaces for the tile actually launched
+    (ADVICE r4).  Plans recorded before the change keep their tapes: release_plans() / a fresh Predictor re-record
+    them."""
+    global _TILE_GEN
+    _TILE_GEN += 1
     if igemm is not None:
         _query("seg_igemm_force_tile", int(igemm))
     if igemm2 is not None:
@@ -193,27 +228,13 @@ class ConvOp:
         # xform: the producer op whose BN + act this op applies to its input on load
         self.lazy = False
         self.xform = xform
-        # packed weights (Program.pack): forward [Cout][ldk_f] (None: a 1x1 conv uses the
-        # weight as is), data gradient [Cin][ldk_d]; depthwise: wk_f = [9][C]
+        # forward / data gradient (None: the first conv) / weight gradient Route (pick_routes) and the packed
+        # weights the first two read (Program._build_pack, in the Route's layout; None: its mode is None)
+        self.route_f = self.route_d = self.route_w = None
         self.wk_f = self.wk_d = None
-        self.ldk_f = self.ldk_d = 0
-        # BN-folded inference weights (Program.fold): fk [Cout][Cin/g][ks][ks], fb [r4(Cout)], fk_pack
+        # BN-folded inference weights (Program.fold): fk [Cout][Cin/g][ks][ks], fb [r4(Cout)], fk_pack [Cout][ldk_f]
         self.fk = self.fb = self.fk_pack = None
-        # Winograd F(2x2,3x3) (seg_conv_wino) for the forward / data gradient, chosen by
-        # seg_conv_wino_pick at pack time; U_f [16][Cout][cin_pad], U_d [16][Cin][r4(Cout)]
-        self.wino_f = self.wino_d = self.wino_w = False
-        self.wino_ff = self.wino_fd = False  # ... on the fused kernel (seg_conv_wino_fused: no M workspace)
-        # LDS-halo direct 3x3 (seg_conv_halo) for the forward / data gradient of narrow convs
-        self.halo_f = self.halo_d = False
-        self.w2 = False  # weight gradient on seg_conv_wgrad2_bf16io (narrow bf16io 3x3)
-        # bf16 math (Program.math == "bf16"): seg_conv_igemm_bf16 / seg_conv_wgrad_bf16
-        self.bf = False
-        # bf16io: wk_f / wk_d packed as bf16 for seg_conv_igemm_bf16io_w16 (Program._build_pack)
-        self.w16_f = self.w16_d = False
-        # bf16io deep convs on seg_conv_igemm2_bf16io (igemm2_plan tuples, chosen at pack time)
-        self.ig2_f = self.ig2_d = None
-        # thin-K 1x1 forward / data gradient on seg_conv_pw (K <= 32, N <= 192; chosen at pack time)
-        self.pw_f = self.pw_d = False
+        self.ldk_f = 0
         self.ks = conv.kernel_size[0]
         self.stride = conv.stride[0]
         self.pad = conv.padding[0]
@@ -235,78 +256,42 @@ class ConvOp:
             ps += [self.bn.weight, self.bn.bias]
         return ps
 
+    def _launch(self, rt, r, sp, sld, g, K, wk, dp, o, C, bias, addp, add_ld, statp, xf, stride, s):
+        """Route `r` of a dense conv: rows of src (pointer sp, row stride sld, image geometry g, K channels) x packed
+        weight -> rows of dst (pointer dp, geometry o, C channels) (+ bias) (+ addend) (+ BN statistics partials).  The
+        argument list of every kernel family, once: the forward calls it with x -> y, the data gradient with dY -> dx
+        (the transposed conv on the data-gradient pack).  xf: the (scale, shift, act) of a lazy producer BN, or None."""
+        wp = wk.data_ptr() if r.mode is not None else self.conv.weight.data_ptr()  # [Cout][Cin][1][1] is a pack already
+        head = (sp, sld, g.N, g.H, g.W, K, wp, r.ldk, bias, dp, o.ld)
+        work = rt.tmp(r.work, zero=r.zero) if r.family in ("wino", "igemm2") else None
+        if r.family == "pw":  # thin-K 1x1 (its producer's lazy BN, if any, on load)
+            args = (sp, sld, g.M, K, wp, r.ldk, bias, dp, o.ld, C, addp, add_ld, statp, *(xf or (None, None, 0)))
+        elif r.family in ("halo", "wino_fused"):
+            args = (*head, C, addp, add_ld, statp)
+        elif r.family == "wino":  # 16 GEMMs + output transform through the M workspace
+            args = (*head, C, addp, add_ld, statp, work.data_ptr())
+        elif r.family == "igemm2":  # bf16io LDS-DMA implicit GEMM (deep 3x3 convs); split-K through the workspace
+            args = (*head, C, self.ks, addp, add_ld, statp, work.data_ptr())
+        else:  # the implicit GEMM; seg_conv_igemm_bf16 is also the folded forward's: + act, residual, its row stride
+            args = (*head, o.H, o.W, C, self.ks, stride, self.pad, addp, add_ld, statp, *(xf or ()),
+                    *((ACT_NONE, None, 1) if r.name == "seg_conv_igemm_bf16" else ()))
+        rt.tcall(r.timer, self.flops(), r.name, *args, s)
+
     # -- forward
     def forward(self, rt):
-        s, y = rt.stream, self.y
-        w = self.conv.weight
-        bias = self.conv.bias.data_ptr() if self.conv.bias is not None else None
+        s, y, i, r = rt.stream, self.y, self.inp, self.route_f
+        stat = None
         if self.kind == "dw":
-            i = self.inp
-            stat = None
-            rt.call(rt.k("seg_dw_fwd"), rt.ptr(i), i.ld, i.N, i.H, i.W, i.C, *self._in_xform(rt),
+            rt.call(r.name, rt.ptr(i), i.ld, i.N, i.H, i.W, i.C, *self._in_xform(rt),
                     self.wk_f.data_ptr(), rt.ptr(y), y.ld, y.H, y.W, self.stride, s)
         else:
-            i = self.inp
-            if self.wk_f is None:
-                ldk, wk_ptr = self.cin, w.data_ptr()  # [Cout][Cin][1][1] already is the packed layout
-            else:
-                ldk, wk_ptr = self.ldk_f, self.wk_f.data_ptr()  # packed by Program.pack at the step start
-            stat = None
-            if self.bn is not None and rt.training:  # BN statistics fused into the conv epilogue
-                if self.pw_f:
-                    tile_rows, ntiles = 128, query("seg_conv_pw_row_tiles", y.M)
-                elif self.ig2_f is not None:
-                    tile_rows, ntiles = self.ig2_f[0], self.ig2_f[1]
-                elif self.wino_f:
-                    ntiles = query("seg_conv_wino_row_tiles", y.N, y.H, y.W)
-                    tile_rows = query("seg_conv_wino_tile_rows")
-                elif self.halo_f:
-                    ntiles, tile_rows = query("seg_conv_halo_row_tiles", y.N, y.H, y.W), 256
-                else:
-                    ntiles, tile_rows = rt.row_tiles(y.M, self.cout)
+            if self.bn is not None and rt.training:  # BN statistics fused into the conv epilogue, one row per tile
+                ntiles, tile_rows = r.tiles
                 stat = rt.tmp(ntiles * 2 * self.cout)
-            statp = stat.data_ptr() if stat is not None else None
-            if self.pw_f:  # thin-K 1x1 (its producer's lazy BN, if any, on load)
-                rt.tcall("igemm1_fwd", self.flops(), rt.k("seg_conv_pw"), rt.ptr(i), i.ld, y.M, self.cin_pad, wk_ptr,
-                         ldk, bias, rt.ptr(y), y.ld, self.cout, None, 0, statp, *self._in_xform(rt), s)
-            elif self.halo_f:
-                name = rt.k("seg_conv_halo") + ("_w16" if self.w16_f else "")
-                rt.tcall("igemm3_fwd", self.flops(), name, rt.ptr(i), i.ld, i.N, i.H, i.W, self.cin_pad,
-                         wk_ptr, ldk, bias, rt.ptr(y), y.ld, self.cout, None, 0, statp, s)
-            elif self.wino_ff and query("seg_conv_wino_fused_ok", i.N, i.H, i.W, i.ld):
-                rt.tcall("wino3_fwd", self.flops(), "seg_conv_wino_fused", rt.ptr(i), i.ld, i.N, i.H, i.W,
-                         self.cin_pad, self.wk_wf.data_ptr(), self.cin_pad, bias, rt.ptr(y), y.ld, self.cout, None, 0,
-                         statp, s)
-            elif self.wino_f:
-                work = rt.tmp(16 * (y.M // 4) * self.cout)
-                rt.tcall("wino3_fwd", self.flops(), "seg_conv_wino", rt.ptr(i), i.ld, i.N, i.H, i.W, self.cin_pad,
-                            self.wk_wf.data_ptr(), self.cin_pad, bias, rt.ptr(y), y.ld, self.cout, None, 0, statp,
-                            work.data_ptr(), s)
-            elif self.ig2_f is not None:  # bf16io LDS-DMA implicit GEMM (deep 3x3 convs)
-                work = rt.tmp(self.ig2_f[3], zero=True)
-                rt.tcall(f"igemm{self.ks}_fwd", self.flops(), "seg_conv_igemm2_bf16io", rt.ptr(i),
-                         i.ld, i.N, i.H, i.W, self.cin_pad, wk_ptr, ldk, bias, rt.ptr(y), y.ld, self.cout, self.ks, None, 0,
-                         statp, work.data_ptr(), s)
-            elif self.xform is not None:  # a conv applying its producer's lazy BN on load
-                name = "seg_conv_igemm_bf16io_xf" if rt.io else "seg_conv_igemm_bf16_xf" if self.bf else "seg_conv_igemm_xf"
-                if rt.io and self.w16_f:
-                    name += "_w16"
-                rt.tcall(f"igemm{self.ks}_fwd", self.flops(), name, rt.ptr(i), i.ld, i.N, i.H, i.W, self.cin_pad, wk_ptr, ldk,
-                         bias, rt.ptr(y), y.ld, y.H, y.W, self.cout, self.ks, self.stride, self.pad, None, 0, statp,
-                         *self._in_xform(rt), s)
-            elif rt.io:
-                rt.tcall(f"igemm{self.ks}_fwd", self.flops(),
-                         "seg_conv_igemm_bf16io_w16" if self.w16_f else "seg_conv_igemm_bf16io", rt.ptr(i), i.ld, i.N, i.H,
-                            i.W, self.cin_pad, wk_ptr, ldk, bias, rt.ptr(y), y.ld, y.H, y.W, self.cout, self.ks,
-                            self.stride, self.pad, None, 0, statp, s)
-            elif self.bf:
-                rt.tcall(f"igemm{self.ks}_fwd", self.flops(), "seg_conv_igemm_bf16", rt.ptr(i), i.ld, i.N, i.H,
-                            i.W, self.cin_pad, wk_ptr, ldk, bias, rt.ptr(y), y.ld, y.H, y.W, self.cout, self.ks,
-                            self.stride, self.pad, None, 0, statp, ACT_NONE, None, 1, s)
-            else:
-                rt.tcall(f"igemm{self.ks}_fwd", self.flops(), "seg_conv_igemm", rt.ptr(i), i.ld, i.N, i.H, i.W,
-                            self.cin_pad, wk_ptr, ldk, bias, rt.ptr(y), y.ld, y.H, y.W, self.cout, self.ks,
-                            self.stride, self.pad, None, 0, statp, s)
+            self._launch(rt, r, rt.ptr(i), i.ld, i, self.cin_pad, self.wk_f, rt.ptr(y), y, self.cout,
+                         self.conv.bias.data_ptr() if self.conv.bias is not None else None, None, 0,
+                         stat.data_ptr() if stat is not None else None,
+                         self._in_xform(rt) if self.xform is not None else None, self.stride, s)
         if self.bn is None:
             return
         bn, C, M = self.bn, self.cout, y.M
@@ -496,38 +481,25 @@ class ConvOp:
                         0, s)
         if self.conv.weight.requires_grad:
             gw = rt.grad_param(self.conv.weight)
-            i = self.inp
-            if self.kind == "dw":
-                nblk = query("seg_dw_wgrad_blocks", y.N, y.H, y.W, self.cout)
-                part = rt.tmp(nblk * 9 * self.cout)
-                rt.call(rt.k("seg_dw_wgrad"), dYp, dY.ld, rt.ptr(i), i.ld, i.N, i.H, i.W, i.C, *self._in_xform(rt), y.H, y.W,
-                     self.stride, part.data_ptr(), s)
-                rt.call("seg_conv_wgrad_reduce", part.data_ptr(), nblk, gw, self.cout, 1, 3, 1, 0, s)
-            elif self.wino_w:
-                form = "seg_conv_wino_wgrad16" if self.wino_w == 2 else "seg_conv_wino_wgrad"
-                splits = query(form + "_splits", y.N, y.H, y.W, self.cin_pad, self.cout)
-                part = rt.tmp(splits * 16 * self.cout * self.cin_pad)
-                rt.tcall("wino3_wgrad", self.flops(), form, dYp, dY.ld, rt.ptr(i), i.ld, y.N, y.H,
-                         y.W, self.cin_pad, self.cout, part.data_ptr(), splits, s)
-                rt.call("seg_conv_wino_wgrad_reduce", part.data_ptr(), splits, gw, self.cout, self.cin, self.cin_pad, 0, s)
-            elif self.w2:  # narrow bf16io 3x3: persistent LDS-halo weight gradient, one slab per block
-                blocks = query("seg_conv_wgrad2_blocks", y.N, y.H, y.W)
-                part = rt.tmp(blocks * self.cout * 9 * self.cin_pad)
-                rt.tcall("igemm3_wgrad", self.flops(), "seg_conv_wgrad2_bf16io", dYp, dY.ld, rt.ptr(i), i.ld, y.N, y.H,
-                         y.W, self.cin_pad, self.cout, part.data_ptr(), s)
-                rt.call("seg_conv_wgrad_reduce", part.data_ptr(), blocks, gw, self.cout, self.cin, 3, 0, 0, s)
-            else:
-                splits = query("seg_conv_wgrad_splits_bf16" if self.bf else "seg_conv_wgrad_splits", M, self.cout,
-                               self.cin_pad, self.ks)
-                part = rt.tmp(splits * self.cout * self.ks * self.ks * self.cin_pad)
-                name = ("seg_conv_wgrad_bf16io" if rt.io else "seg_conv_wgrad_bf16") if self.bf else "seg_conv_wgrad"
-                xf = ()
-                if self.xform is not None:  # X = the producer's lazy BN + act, formed on load
-                    name, xf = name + "_xf", self._in_xform(rt)
-                rt.tcall(f"igemm{self.ks}_wgrad", self.flops(), name, dYp, dY.ld, rt.ptr(i), i.ld,
-                            i.N, i.H, i.W, self.cin_pad, y.H, y.W, self.cout, self.ks, self.stride, self.pad,
-                            part.data_ptr(), splits, *xf, s)
-                rt.call("seg_conv_wgrad_reduce", part.data_ptr(), splits, gw, self.cout, self.cin, self.ks, 0, 0, s)
+            i, r = self.inp, self.route_w
+            slabs = rt.tmp(r.work)  # r.splits slabs of partial sums, summed in a fixed order by the reduce
+            part = slabs.data_ptr()
+            if r.family == "dw":
+                rt.call(r.name, dYp, dY.ld, rt.ptr(i), i.ld, i.N, i.H, i.W, i.C, *self._in_xform(rt), y.H, y.W,
+                        self.stride, part, s)
+                rt.call("seg_conv_wgrad_reduce", part, r.splits, gw, self.cout, 1, 3, 1, 0, s)
+            elif r.family == "igemm":  # with a lazy producer (_xf): X = its BN + act, formed on load
+                rt.tcall(r.timer, self.flops(), r.name, dYp, dY.ld, rt.ptr(i), i.ld, i.N, i.H, i.W, self.cin_pad, y.H,
+                         y.W, self.cout, self.ks, self.stride, self.pad, part, r.splits,
+                         *(self._in_xform(rt) if self.xform is not None else ()), s)
+                rt.call("seg_conv_wgrad_reduce", part, r.splits, gw, self.cout, self.cin, self.ks, 0, 0, s)
+            else:  # 3x3: Winograd F(3x3,2x2) (wino, wino16) / the persistent LDS-halo kernel, one slab per block
+                rt.tcall(r.timer, self.flops(), r.name, dYp, dY.ld, rt.ptr(i), i.ld, y.N, y.H, y.W, self.cin_pad,
+                         self.cout, part, *(() if r.family == "wgrad2" else (r.splits,)), s)
+                if r.family == "wgrad2":
+                    rt.call("seg_conv_wgrad_reduce", part, r.splits, gw, self.cout, self.cin, 3, 0, 0, s)
+                else:
+                    rt.call("seg_conv_wino_wgrad_reduce", part, r.splits, gw, self.cout, self.cin, self.cin_pad, 0, s)
         rt.params_done(self.params(), s)
 
     def _dgrad(self, rt, dY, dYp, s):
@@ -535,64 +507,25 @@ class ConvOp:
         y, i = self.y, self.inp
         if self.kind == "dw":
             acc = rt.begin_write_accumulate(i)
-            rt.call(rt.k("seg_dw_dgrad"), dYp, dY.ld, y.N, y.H, y.W, self.cout, self.wk_f.data_ptr(), rt.gptr(i),
+            rt.call(self.route_d.name, dYp, dY.ld, y.N, y.H, y.W, self.cout, self.wk_f.data_ptr(), rt.gptr(i),
                     i.ld, i.H, i.W, self.stride, acc, s)
         else:
             if self.stride != 1:
                 raise NotImplementedError("data gradient of a strided dense conv")
             kin = r4(self.cout)  # dY channels padded to 4 (the C=10 head)
-            bo = None
             add_ptr, add_ld = rt.begin_write_add(i)
-            # seg_conv_pw / seg_conv_igemm2 read the addend as 16-byte row vectors
-            add16 = add_ptr is None or (add_ld % (16 // rt.es) == 0 and add_ptr % 16 == 0)
-            if self.pw_d and add16:  # thin-K 1x1 data gradient
-                rt.tcall("igemm1_dgrad", self.flops(), rt.k("seg_conv_pw"), dYp, dY.ld, y.M, kin, self.wk_d.data_ptr(),
-                         self.ldk_d, None, rt.gptr(i), i.ld, self.cin, add_ptr, add_ld, None, None, None, 0, s)
-            elif self.halo_d:
-                rt.tcall("igemm3_dgrad", self.flops(), rt.k("seg_conv_halo") + ("_w16" if self.w16_d else ""), dYp,
-                         dY.ld, y.N, y.H, y.W, kin,
-                            self.wk_d.data_ptr(), self.ldk_d, None, rt.gptr(i), i.ld, self.cin, add_ptr, add_ld, None, s)
-            elif self.wino_fd and query("seg_conv_wino_fused_ok", y.N, y.H, y.W, dY.ld):
-                rt.tcall("wino3_dgrad", self.flops(), "seg_conv_wino_fused", dYp, dY.ld, y.N, y.H, y.W, kin,
-                         self.wk_wd.data_ptr(), kin, None, rt.gptr(i), i.ld, self.cin, add_ptr, add_ld, None, s)
-            elif self.wino_d:
-                work = rt.tmp(16 * (y.M // 4) * self.cin)
-                rt.tcall("wino3_dgrad", self.flops(), "seg_conv_wino", dYp, dY.ld, y.N, y.H, y.W, kin,
-                            self.wk_wd.data_ptr(), kin, None, rt.gptr(i), i.ld, self.cin, add_ptr, add_ld, None,
-                            work.data_ptr(), s)
-            elif self.ig2_d is not None and add16:
-                work = rt.tmp(self.ig2_d[3], zero=True)
-                rt.tcall(f"igemm{self.ks}_dgrad", self.flops(), "seg_conv_igemm2_bf16io", dYp, dY.ld, y.N, y.H, y.W, kin,
-                         self.wk_d.data_ptr(), self.ldk_d, None, rt.gptr(i), i.ld, self.cin, self.ks, add_ptr, add_ld,
-                         None, work.data_ptr(), s)
-            elif rt.io:
-                bo = self._bnout(rt, i)
-                if bo is not None:  # + the BN-backward partials of the layer whose dA this completes
-                    rt.tcall(f"igemm{self.ks}_dgrad", self.flops(),
-                             "seg_conv_igemm_bnout_bf16io_w16" if self.w16_d else "seg_conv_igemm_bnout_bf16io", dYp,
-                             dY.ld, y.N, y.H, y.W, kin, self.wk_d.data_ptr(), self.ldk_d, rt.gptr(i), i.ld, self.cin,
-                             self.ks, add_ptr, add_ld, *bo[0], s)
-                else:
-                    rt.tcall(f"igemm{self.ks}_dgrad", self.flops(),
-                             "seg_conv_igemm_bf16io_w16" if self.w16_d else "seg_conv_igemm_bf16io", dYp, dY.ld, y.N, y.H,
-                             y.W, kin, self.wk_d.data_ptr(), self.ldk_d, None, rt.gptr(i), i.ld, i.H, i.W, self.cin,
-                             self.ks, 1, self.pad, add_ptr, add_ld, None, s)
-            elif self.bf:
-                rt.tcall(f"igemm{self.ks}_dgrad", self.flops(), "seg_conv_igemm_bf16", dYp, dY.ld, y.N, y.H, y.W,
-                            kin, self.wk_d.data_ptr(), self.ldk_d, None, rt.gptr(i), i.ld, i.H, i.W, self.cin,
-                            self.ks, 1, self.pad, add_ptr, add_ld, None, ACT_NONE, None, 1, s)
-            else:
-                bo = self._bnout(rt, i)
-                if bo is not None:
-                    rt.tcall(f"igemm{self.ks}_dgrad", self.flops(), "seg_conv_igemm_bnout", dYp, dY.ld, y.N, y.H, y.W,
-                             kin, self.wk_d.data_ptr(), self.ldk_d, rt.gptr(i), i.ld, self.cin, self.ks, add_ptr, add_ld,
-                             *bo[0], s)
-                else:
-                    rt.tcall(f"igemm{self.ks}_dgrad", self.flops(), "seg_conv_igemm", dYp, dY.ld, y.N, y.H, y.W, kin,
-                             self.wk_d.data_ptr(), self.ldk_d, None, rt.gptr(i), i.ld, i.H, i.W, self.cin, self.ks, 1,
-                             self.pad, add_ptr, add_ld, None, s)
-            if bo is not None:  # the partials are valid while this write is the buffer's last
-                rt.mark_written(i)
+            r = self.route_d
+            # seg_conv_pw / seg_conv_igemm2 read the addend as 16-byte row vectors: else the implicit GEMM
+            if r.fallback is not None and add_ptr is not None and (add_ld % (16 // rt.es) or add_ptr % 16):
+                r = r.fallback
+            bo = self._bnout(rt, i) if r.bnout is not None else None
+            if bo is None:
+                self._launch(rt, r, dYp, dY.ld, y, kin, self.wk_d, rt.gptr(i), i, self.cin, None, add_ptr, add_ld,
+                             None, None, 1, s)
+            else:  # + the BN-backward partials of the layer whose dA this completes
+                rt.tcall(r.timer, self.flops(), r.bnout, dYp, dY.ld, y.N, y.H, y.W, kin, self.wk_d.data_ptr(), r.ldk,
+                         rt.gptr(i), i.ld, self.cin, self.ks, add_ptr, add_ld, *bo[0], s)
+                rt.mark_written(i)  # the partials are valid while this write is the buffer's last
                 rt.bn_parts[id(bo[1])][2] = rt.wgen[i.buf]
                 return
         rt.mark_written(i)
@@ -775,121 +708,36 @@ class Program:
 
     def pack(self, rt):
         """Repack every conv weight for this step (one seg_pack_batch launch on the run's
-        stream).  The packed buffers and the device job table are built once and rebuilt
-        only when a weight's storage moves (e.g. model.to())."""
+        stream).  The routes, the packed buffers and the device job table are built once and
+        rebuilt only when a weight's storage moves (e.g. model.to()) or a tile is forced."""
         convs = [op for op in self.ops if isinstance(op, ConvOp)]
-        key = tuple(op.conv.weight.data_ptr() for op in convs)
+        key = (_TILE_GEN, *(op.conv.weight.data_ptr() for op in convs))
         if getattr(self, "_pack_key", None) != key:
             self._build_pack(convs, key)
         if self._njobs:
             rt.call("seg_pack_batch", self._jobs.data_ptr(), self._njobs, self._pack_blocks, rt.stream)
 
     def _build_pack(self, convs, key):
-        import numpy as np
-        if self.math == "f16":
-            raise NotImplementedError("f16 conv math is the inference configuration (Predictor(model, math='f16')); "
-                                      "train with 'f32' or 'bf16'")
-        jobs, max_elems = [], 0
+        """Pick the routes, then allocate the packed weights they read and build the pack job table."""
+        pick_routes(self)
+        jobs = []
         for op in convs:
             w = op.conv.weight
-            dev = w.device
-            if op.kind == "dw":
-                op.wk_f = torch.empty(9 * op.cout, device=dev, dtype=torch.float32)
-                jobs.append((w.data_ptr(), op.wk_f.data_ptr(), op.cout, 1, 3, 9, 2, 1))
-                max_elems = max(max_elems, 9 * op.cout)
-                continue
-            y = op.y
-            op.bf = self.math in ("bf16", "bf16io")
-            if op.bf:
-                # bf16 math: every dense / pointwise conv (fwd, dgrad, wgrad) on the bf16 implicit GEMM
-                op.wino_f = op.wino_d = op.wino_w = op.halo_f = op.halo_d = False
-                op.wino_ff = op.wino_fd = False
-                # narrow bf16io 3x3 weight gradients on seg_conv_wgrad2_bf16io (SEG_WGRAD2=0: the implicit GEMM)
-                op.w2 = (self.math == "bf16io" and WGRAD2 and op.ks == 3 and op.stride == 1 and op.pad == 1
-                         and op.xform is None and op.cin_pad == op.cin and y.ld % 8 == 0 and op.inp.ld % 8 == 0
-                         and op.inp.off % 8 == 0
-                         and bool(query("seg_conv_wgrad2_ok", y.N, y.H, y.W, op.cin_pad, op.cout)))
-                if self.math == "bf16io" and op.ks == 3 and op.stride == 1 and op.pad == 1:
-                    # narrow convs: the LDS-halo direct conv (seg_conv_halo_bf16io): 8-channel slots
-                    op.halo_f = (op.cin_pad % 8 == 0 and HALO_BF16
-                                 and bool(query("seg_conv_halo_pick", y.N, y.H, y.W, op.cin_pad, op.cout)))
-                    op.halo_d = (not op.first and r4(op.cout) % 8 == 0 and HALO_BF16
-                                 and bool(query("seg_conv_halo_pick", y.N, y.H, y.W, r4(op.cout), op.cin)))
-                # bf16io implicit-GEMM and LDS-halo launches take bf16 packed weights (seg_conv_*_bf16io_w16:
-                # half the weight bytes every M tile / pixel tile re-reads)
-                w16f = w16d = self.math == "bf16io" and W16
-                op.w16_f, op.w16_d = w16f, w16d
-                # the deep 3x3 convs on seg_conv_igemm2_bf16io
-                op.ig2_f = op.ig2_d = None
-                # beyond IGEMM2_MAX_ROWS only GEMMs whose N fills the 8-wave tiles (N % 128 == 0: UNet's deep levels)
-                wide = y.M > IGEMM2_MAX_ROWS and IGEMM2_WIDE
-                if (w16f and IGEMM2 and op.ks == 3 and op.stride == 1 and op.pad == 1
-                        and (y.M <= IGEMM2_MAX_ROWS or wide)):
-                    i = op.inp  # 16-byte rows: ld and channel offset multiples of 8 elements
-                    rows16 = i.ld % 8 == 0 and i.off % 8 == 0 and y.ld % 8 == 0 and y.off % 8 == 0
-                    if (rows16 and not op.halo_f and op.xform is None and op.cin_pad == op.cin
-                            and (not wide or op.cout % 128 == 0)):
-                        op.ig2_f = igemm2_plan(y.M, op.cout, op.cin_pad, op.ks)
-                    if (rows16 and not op.first and not op.halo_d and op.cout % 8 == 0
-                            and (not wide or op.cin % 128 == 0)):
-                        op.ig2_d = igemm2_plan(y.M, op.cin, op.cout, op.ks)
-                if w16f:
-                    op.pw_f, op.pw_d = _pw_pick(op, 8)
-                if w16f or not (op.ks == 1 and op.cin_pad == op.cin):
-                    op.ldk_f = r8(op.ks * op.ks * op.cin_pad) if w16f else r4(op.ks * op.ks * op.cin_pad)
-                    op.wk_f = torch.empty(op.cout * op.ldk_f, device=dev,
-                                          dtype=torch.bfloat16 if w16f else torch.float32)
-                    jobs.append((w.data_ptr(), op.wk_f.data_ptr(), op.cout, op.cin, op.ks, op.ldk_f, 16 if w16f else 0,
-                                 op.cin_pad))
-                    max_elems = max(max_elems, op.cout * op.ldk_f)
-                if not op.first:
-                    kin = r4(op.cout)
-                    op.ldk_d = r8(op.ks * op.ks * kin) if w16d else r4(op.ks * op.ks * kin)
-                    op.wk_d = torch.empty(op.cin * op.ldk_d, device=dev, dtype=torch.bfloat16 if w16d else torch.float32)
-                    jobs.append((w.data_ptr(), op.wk_d.data_ptr(), op.cout, op.cin, op.ks, op.ldk_d, 17 if w16d else 1,
-                                 kin))
-                    max_elems = max(max_elems, op.cin * op.ldk_d)
-                continue
-            op.pw_f, op.pw_d = _pw_pick(op, 4)
-            dense3 = op.ks == 3 and op.stride == 1 and op.pad == 1
-            wino_ok = dense3 and WINOGRAD
-            # seg_conv_wino_pick: 1 = the two-launch form, 2 = the fused kernel
-            pf = query("seg_conv_wino_pick", y.N, y.H, y.W, op.cin_pad, op.cout) if wino_ok and WINOGRAD_FWD else 0
-            pd = (query("seg_conv_wino_pick", y.N, y.H, y.W, r4(op.cout), op.cin)
-                  if wino_ok and WINOGRAD_DGRAD and not op.first else 0)
-            op.wino_f, op.wino_ff = pf != 0, pf == 2
-            op.wino_d, op.wino_fd = pd != 0, pd == 2
-            # seg_conv_wino_wgrad_pick: 2 = the all-points kernel (seg_conv_wino_wgrad16), 1 = the per-point one
-            op.wino_w = (query("seg_conv_wino_wgrad_pick", y.N, y.H, y.W, op.cin_pad, op.cout)
-                         if wino_ok and WINOGRAD_WGRAD and op.xform is None else 0)
-            if op.wino_w == 2 and not WINO_WGRAD16:  # A/B switch: the round-5 rule (per-point kernel, deep convs)
-                T = y.N * (y.H // 2) * (y.W // 2)
-                deep = op.cin_pad >= 128 and op.cout >= 128 and (T >= 65536 or min(op.cin_pad, op.cout) >= 256)
-                op.wino_w = 1 if deep else 0
-            op.halo_f = (dense3 and not op.wino_f
-                         and bool(query("seg_conv_halo_pick", y.N, y.H, y.W, op.cin_pad, op.cout)))
-            op.halo_d = (dense3 and not op.first and not op.wino_d
-                         and bool(query("seg_conv_halo_pick", y.N, y.H, y.W, r4(op.cout), op.cin)))
-            if op.wino_f:
-                op.wk_wf = torch.empty(16 * op.cout * op.cin_pad, device=dev, dtype=torch.float32)
-                jobs.append((w.data_ptr(), op.wk_wf.data_ptr(), op.cout, op.cin, 3, op.cin_pad, 3, op.cin_pad))
-                max_elems = max(max_elems, op.cout * op.cin_pad)
-            elif not (op.ks == 1 and op.cin_pad == op.cin):
-                op.ldk_f = r4(op.ks * op.ks * op.cin_pad)
-                op.wk_f = torch.empty(op.cout * op.ldk_f, device=dev, dtype=torch.float32)
-                jobs.append((w.data_ptr(), op.wk_f.data_ptr(), op.cout, op.cin, op.ks, op.ldk_f, 0, op.cin_pad))
-                max_elems = max(max_elems, op.cout * op.ldk_f)
-            if op.wino_d:
-                kin = r4(op.cout)
-                op.wk_wd = torch.empty(16 * op.cin * kin, device=dev, dtype=torch.float32)
-                jobs.append((w.data_ptr(), op.wk_wd.data_ptr(), op.cout, op.cin, 3, kin, 4, kin))
-                max_elems = max(max_elems, op.cin * kin)
-            elif not op.first:
-                kin = r4(op.cout)
-                op.ldk_d = r4(op.ks * op.ks * kin)
-                op.wk_d = torch.empty(op.cin * op.ldk_d, device=dev, dtype=torch.float32)
-                jobs.append((w.data_ptr(), op.wk_d.data_ptr(), op.cout, op.cin, op.ks, op.ldk_d, 1, kin))
-                max_elems = max(max_elems, op.cin * op.ldk_d)
+            op.wk_f = op.wk_d = None
+            for d, r in enumerate((op.route_f, op.route_d)):
+                if r is None or r.mode is None:
+                    continue
+                lay = r.mode & 15
+                rows = op.cin if lay in (1, 4) else op.cout  # [rows][ldk]; Winograd: one such matrix per point
+                wk = torch.empty((16 if lay in (3, 4) else 1) * rows * r.ldk, device=w.device,
+                                 dtype=torch.bfloat16 if r.mode & 16 else torch.float32)
+                kin = 1 if lay == 2 else r4(op.cout) if d else op.cin_pad
+                jobs.append((w.data_ptr(), wk.data_ptr(), op.cout, 1 if lay == 2 else op.cin, op.ks, r.ldk, r.mode,
+                             kin))
+                if d:
+                    op.wk_d = wk
+                else:
+                    op.wk_f = wk
         self._jobs, self._njobs, self._pack_blocks = pack_table(jobs, convs[0].conv.weight.device)
         self._pack_key = key
 
@@ -978,6 +826,103 @@ def pack_table(jobs, device):
     t = np.array(rows, dtype=np.dtype(_PACK_JOB))
     assert t.dtype.itemsize == 48
     return torch.from_numpy(t.view(np.uint8).copy()).to(device), len(rows), blk
+
+
+def pick_routes(prog: Program) -> None:
+    """Give every ConvOp of `prog` its forward / data-gradient / weight-gradient Route.  A pure function of the
+    program's shapes and conv math, the engine switches (SEG_*, the diagnostics constants) and the library's host-side
+    queries: no tensor, no device call.  The one place where a kernel is wired to the layers it runs."""
+    if prog.math == "f16":
+        raise NotImplementedError("f16 conv math is the inference configuration (Predictor(model, math='f16')); "
+                                  "train with 'f32' or 'bf16'")
+    sfx = "_bf16io" if prog.math == "bf16io" else ""
+    for op in prog.ops:
+        if not isinstance(op, ConvOp):
+            continue
+        if op.kind == "dw":
+            nblk = query("seg_dw_wgrad_blocks", op.y.N, op.y.H, op.y.W, op.cout)
+            op.route_f = Route("dw", "seg_dw_fwd" + sfx, None, 2, 9)  # [9][C], read by the data gradient too
+            op.route_d = Route("dw", "seg_dw_dgrad" + sfx, None, None, 9)
+            op.route_w = Route("dw", "seg_dw_wgrad" + sfx, None, work=nblk * 9 * op.cout, splits=nblk)
+        else:
+            op.route_f = _pick_conv(prog.math, op, 0)
+            op.route_d = None if op.first else _pick_conv(prog.math, op, 1)  # no data gradient for the model input
+            op.route_w = _pick_wgrad(prog.math, op)
+
+
+def _pick_conv(math, op, d):
+    """Route of a dense conv's forward (d = 0: x [M][K = cin_pad] -> y [M][C = Cout]) or data gradient (d = 1: the
+    transposed conv, dY [M][K = r4(Cout)] -> dx [M][C = Cin]).  Precedence: thin-K 1x1, Winograd (f32), LDS halo (f32:
+    where Winograd declined), igemm2 (where the halo kernel declined), the implicit GEMM (any shape)."""
+    y, i, ks = op.y, op.inp, op.ks
+    io, bf = math == "bf16io", math != "f32"
+    K, C = (r4(op.cout), op.cin) if d else (op.cin_pad, op.cout)
+    kind, sfx = ("dgrad" if d else "fwd"), ("_bf16io" if io else "")
+    dense3 = ks == 3 and op.stride == 1 and op.pad == 1
+    # bf16io launches take bf16 packed weights (_w16: half the weight bytes every M tile / pixel tile re-reads)
+    w16 = io and W16
+    mode, ldk = d + (16 if w16 else 0), (r8 if w16 else r4)(ks * ks * K)
+    if not d and not w16 and ks == 1 and K == op.cin:
+        mode, ldk = None, op.cin  # [Cout][Cin][1][1] already is the forward's packed layout
+    name = "seg_conv_igemm" + (sfx or ("_bf16" if bf else ""))
+    if not d and op.xform is not None:  # a conv applying its producer's lazy BN on load
+        name += "_xf"
+    igemm = Route("igemm", name + ("_w16" if w16 else ""), f"igemm{ks}_{kind}", mode, ldk,
+                  None if d else Run.row_tiles(y.M, C),
+                  bnout="seg_conv_igemm_bnout" + sfx + ("_w16" if w16 else "") if d and (io or not bf) else None)
+    r = igemm
+    # seg_conv_wino_pick: 1 = the two-launch form, 2 = the fused kernel (no M workspace), if the rows allow it
+    wino = (query("seg_conv_wino_pick", y.N, y.H, y.W, K, C)
+            if dense3 and not bf and WINOGRAD and (WINOGRAD_DGRAD if d else WINOGRAD_FWD) else 0)
+    wide = y.M > IGEMM2_MAX_ROWS  # igemm2 beyond it: only GEMMs whose N fills the 8-wave tiles (UNet's deep levels)
+    if (w16 or not bf) and _pw_pick(op, 8 if io else 4)[d]:
+        r = Route("pw", "seg_conv_pw" + sfx, f"igemm1_{kind}", mode, ldk, (query("seg_conv_pw_row_tiles", y.M), 128),
+                  fallback=igemm if d else None)
+    elif wino:
+        tiles = (query("seg_conv_wino_row_tiles", y.N, y.H, y.W), query("seg_conv_wino_tile_rows"))
+        src_ld = (r4(op.cout) if op.bn is not None else op.out.ld) if d else i.ld  # of dY: ConvOp.backward
+        if wino == 2 and query("seg_conv_wino_fused_ok", y.N, y.H, y.W, src_ld):
+            r = Route("wino_fused", "seg_conv_wino_fused", f"wino3_{kind}", 3 + d, K, tiles)
+        else:
+            r = Route("wino", "seg_conv_wino", f"wino3_{kind}", 3 + d, K, tiles, work=16 * (y.M // 4) * C)
+    elif (dense3 and (not bf or (io and HALO_BF16 and K % 8 == 0))  # bf16io: 8-channel slots
+            and query("seg_conv_halo_pick", y.N, y.H, y.W, K, C)):
+        r = Route("halo", "seg_conv_halo" + sfx + ("_w16" if w16 else ""), f"igemm3_{kind}", mode, ldk,
+                  (query("seg_conv_halo_row_tiles", y.N, y.H, y.W), 256))
+    elif (w16 and IGEMM2 and dense3 and (not wide or (IGEMM2_WIDE and C % 128 == 0))
+            and i.ld % 8 == 0 and i.off % 8 == 0 and y.ld % 8 == 0 and y.off % 8 == 0  # 16-byte rows
+            and (op.cout % 8 == 0 if d else op.xform is None and K == op.cin)):
+        plan = igemm2_plan(y.M, C, K, ks)
+        if plan is not None:
+            r = Route("igemm2", "seg_conv_igemm2_bf16io", f"igemm{ks}_{kind}", mode, ldk, (plan[1], plan[0]),
+                      work=plan[3], zero=True, fallback=igemm if d else None)
+    return r if not d and op.bn is not None else r._replace(tiles=None)
+
+
+def _pick_wgrad(math, op):
+    """Weight-gradient Route of a dense conv: Winograd F(3x3,2x2) (f32), the persistent LDS-halo kernel (narrow
+    bf16io 3x3), else the split-K implicit GEMM."""
+    y, i, ks, K, cout = op.y, op.inp, op.ks, op.cin_pad, op.cout
+    io, bf = math == "bf16io", math != "f32"
+    dense3 = ks == 3 and op.stride == 1 and op.pad == 1
+    if dense3 and not bf and WINOGRAD and WINOGRAD_WGRAD and op.xform is None:
+        # seg_conv_wino_wgrad_pick: 2 = the all-points kernel (seg_conv_wino_wgrad16), 1 = the per-point one
+        p = query("seg_conv_wino_wgrad_pick", y.N, y.H, y.W, K, cout)
+        if p == 2 and not WINO_WGRAD16:  # A/B switch: the round-5 rule (per-point kernel, deep convs)
+            T = y.N * (y.H // 2) * (y.W // 2)
+            p = int(K >= 128 and cout >= 128 and (T >= 65536 or min(K, cout) >= 256))
+        if p:
+            name = "seg_conv_wino_wgrad16" if p == 2 else "seg_conv_wino_wgrad"
+            splits = query(name + "_splits", y.N, y.H, y.W, K, cout)
+            return Route("wino16" if p == 2 else "wino", name, "wino3_wgrad", work=splits * 16 * cout * K,
+                         splits=splits)
+    if (io and WGRAD2 and dense3 and op.xform is None and K == op.cin and y.ld % 8 == 0 and i.ld % 8 == 0
+            and i.off % 8 == 0 and query("seg_conv_wgrad2_ok", y.N, y.H, y.W, K, cout)):
+        blocks = query("seg_conv_wgrad2_blocks", y.N, y.H, y.W)
+        return Route("wgrad2", "seg_conv_wgrad2_bf16io", "igemm3_wgrad", work=blocks * cout * 9 * K, splits=blocks)
+    splits = query("seg_conv_wgrad_splits_bf16" if bf else "seg_conv_wgrad_splits", y.M, cout, K, ks)
+    name = "seg_conv_wgrad" + ("_bf16io" if io else "_bf16" if bf else "") + ("_xf" if op.xform is not None else "")
+    return Route("igemm", name, f"igemm{ks}_wgrad", work=splits * cout * ks * ks * K, splits=splits)
 
 
 def _cna(prog, m: ConvBNReLU6, inp, out=None, kind=None, xform=None):
