@@ -631,6 +631,45 @@ int seg_mbconv_f16(const float* x, long ldx, int N, int H, int W, int Cin, const
                    const float* res, long ldres, float* out, long ldo, float* work, unsigned* cnt,
                    hipStream_t stream);
 
+/* ---- overlay post-processing (inference.py:72-146, overlay_predictions; csrc/overlay.hip) --------
+ * The reference's per-frame OpenCV stage on the GPU: road = (cls == 1) -> 5x5 close -> 8-connected
+ * components -> largest -> cleaned = cls with that component painted 1 -> class colours -> car blobs
+ * (components of cleaned == 2) with boxes -> 0.6 / 0.4 blend -> box outlines.  All entries are
+ * stream-ordered with no host round trip; every result is independent of scheduling.  Frames, masks and
+ * results are contiguous ([Hf][Wf][3] / [Hf][Wf] bytes); Hf * Wf < 2^31.
+ *   labels: int [Hf][Wf], the smallest linear index y*Wf + x of the pixel's component, background -1;
+ *   boxes:  int [max_boxes][5] = x, y, w, h, area (pixel count) of the components with area > min_area, in
+ *           ascending label order; count[2] = {stored (<= max_boxes), passed};
+ *   table:  [ncolors][4] bytes = the class's colour in the frame's channel order + a "listed" flag; a class
+ *           that is not listed (or >= ncolors) keeps the frame's pixel;
+ *   work:   seg_overlay_workspace_bytes(Hf, Wf, max_boxes) bytes (0 = invalid sizes), 16-byte aligned,
+ *           caller-owned, needs no clearing between frames.
+ * seg_cc_tile_h / _w: the labelling tile (tests place shapes on its borders). */
+int seg_cc_tile_h(void);
+int seg_cc_tile_w(void);
+long seg_overlay_workspace_bytes(int Hf, int Wf, int max_boxes);
+/* out = 5x5 close (all-ones element, one iteration, cv2's constant border) of (mask == class_id), 0 / 1 */
+int seg_morph_close5(const unsigned char* mask, int Hf, int Wf, int class_id, unsigned char* out,
+                     hipStream_t stream);
+int seg_cc_label8(const unsigned char* mask, int Hf, int Wf, int* labels, hipStream_t stream);
+/* out[2] = root, area of the largest component (ties: the smaller root); {-1, 0} without foreground */
+int seg_cc_largest(const int* labels, int Hf, int Wf, int* out, void* work, long work_bytes, hipStream_t stream);
+int seg_cc_boxes(const int* labels, int Hf, int Wf, int min_area, int max_boxes, int* boxes, int* count, void* work,
+                 long work_bytes, hipStream_t stream);
+/* result = rint(float(frame) * 0.6f + float(overlay) * 0.4f), overlay = table[cleaned] (cv2.addWeighted's
+ * 8-bit path as published: float32 products and sum, no fused multiply-add, half to even) */
+int seg_overlay_blend(const unsigned char* frame, const unsigned char* cleaned, int Hf, int Wf,
+                      const unsigned char* table, int ncolors, unsigned char* result, hipStream_t stream);
+/* per stored box: the pixels of [x, x+w] x [y, y+h] (clipped) outside [x+2, x+w-2] x [y+2, y+h-2] become
+ * blend(frame, (0, 255, 0)) */
+int seg_overlay_outline(const unsigned char* frame, int Hf, int Wf, const int* boxes, const int* count,
+                        int max_boxes, unsigned char* result, hipStream_t stream);
+/* the whole stage on the class mask cls (what seg_argmax_nearest writes): 16 launches, one chain */
+int seg_overlay_frame(const unsigned char* frame, const unsigned char* cls, int Hf, int Wf,
+                      const unsigned char* table, int ncolors, int min_area, int max_boxes, int draw_boxes,
+                      unsigned char* cleaned, unsigned char* result, int* boxes, int* count, void* work,
+                      long work_bytes, hipStream_t stream);
+
 /* Build identity (host only): copies the SHA-256 (64 hex chars + NUL) of the sources this
  * library was built from -- every csrc file, this header, compiler and flags
  * (seg_amd/build.py source_hash) -- into out when cap > 64; returns the length.  The

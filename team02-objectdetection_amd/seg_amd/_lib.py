@@ -124,6 +124,17 @@ PROTOTYPES = {
                             _V]),
     "seg_conv_igemm_bnout": (_I, [_V, _L, _I, _I, _I, _I, _V, _I, _V, _L, _I, _I, _V, _L, _V, _L, _V, _V, _V, _I,
                                   _V, _V]),
+    # overlay post-processing (csrc/overlay.hip, seg_amd/overlay.py)
+    "seg_cc_tile_h": (_I, []),
+    "seg_cc_tile_w": (_I, []),
+    "seg_overlay_workspace_bytes": (_L, [_I, _I, _I]),
+    "seg_morph_close5": (_I, [_V, _I, _I, _I, _V, _V]),
+    "seg_cc_label8": (_I, [_V, _I, _I, _V, _V]),
+    "seg_cc_largest": (_I, [_V, _I, _I, _V, _V, _L, _V]),
+    "seg_cc_boxes": (_I, [_V, _I, _I, _I, _I, _V, _V, _V, _L, _V]),
+    "seg_overlay_blend": (_I, [_V, _V, _I, _I, _V, _I, _V, _V]),
+    "seg_overlay_outline": (_I, [_V, _I, _I, _V, _V, _I, _V, _V]),
+    "seg_overlay_frame": (_I, [_V, _V, _I, _I, _V, _I, _I, _I, _I, _V, _V, _V, _V, _V, _L, _V]),
 }
 # bf16-storage variants: same C signature shape as their fp32 namesakes (pointers stay void*)
 for _n in ("seg_add", "seg_bn_stats", "seg_bn_apply", "seg_bn_backward", "seg_colsum", "seg_dw_fwd", "seg_dw_dgrad",

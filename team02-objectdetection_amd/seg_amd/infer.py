@@ -5,7 +5,8 @@ The reference loop (inference.py:150-170) does, per video frame:
     road_predictions = model(img_tensor)               # :162-163 eval forward under no_grad
     _, cls = torch.max(road_predictions, dim=1)        # :64     (inside overlay_predictions)
     cls = cv2.resize(cls.astype(uint8), (W, H), INTER_NEAREST)   # :68-70
-and then OpenCV post-processing / display (out of scope, host GUI code).
+and then overlay_predictions' OpenCV post-processing (inference.py:72-146), which
+seg_amd/overlay.py runs on the GPU (`Predictor(..., overlay=True)`), and the display.
 
 `Predictor` runs all of that on the MI355X as four stages over static buffers,
 captured once into a HIP graph (torch.cuda.CUDAGraph drives hipGraph on ROCm):
@@ -64,9 +65,14 @@ class Predictor:
     math="f16" runs every folded conv on fp16 operands (BASELINE configs[3]).
     Weights are folded at construction; call `refresh()` after changing the
     model's parameters or running statistics (e.g. load_state_dict).
+
+    overlay=True (or an `Overlay` instance) appends overlay_predictions' post-processing
+    (seg_amd/overlay.py) to the launch sequence and the graph:
+    result, detected_objects = predictor.annotate(frame); `__call__` still returns the mask.
     """
 
-    def __init__(self, model, frame_hw=(720, 1280), target_size=(256, 128), graph: bool = True, math: str = "f32"):
+    def __init__(self, model, frame_hw=(720, 1280), target_size=(256, 128), graph: bool = True, math: str = "f32",
+                 overlay=False):
         p = next(model.parameters())
         if not p.is_cuda:
             raise RuntimeError("Predictor runs on the MI355X HIP path only; move the model to 'cuda' first")
@@ -86,6 +92,12 @@ class Predictor:
         self.graph = None
         self.refresh()
         self.stem_pre = self.prog.stem_pre() if (engine.STEM_PRE and math == "f16") else None
+        self.overlay = None
+        if overlay is not False and overlay is not None:
+            from .overlay import Overlay
+            self.overlay = Overlay(frame_hw, device=self.device) if overlay is True else overlay
+            if not isinstance(self.overlay, Overlay) or (self.overlay.Hf, self.overlay.Wf) != (self.Hf, self.Wf):
+                raise ValueError(f"overlay must be True or an Overlay for {self.Hf}x{self.Wf} frames")
         if graph:
             self._capture()
 
@@ -112,6 +124,8 @@ class Predictor:
         Ho, Wo = prog.out_hw
         call("seg_argmax_nearest", rt.ptr(lo), lo.ld, 1, lo.H, lo.W, lo.C, Ho, Wo, self.mask.data_ptr(), self.Hf,
              self.Wf, s)
+        if self.overlay is not None:
+            self.overlay.launch(self.frame, self.mask, s)
 
     def _capture(self):
         side = torch.cuda.Stream(self.device)
@@ -148,6 +162,14 @@ class Predictor:
         if frame is not None:
             self.set_frame(frame)
         return self.step()
+
+    def annotate(self, frame=None):
+        """(result, detected_objects) of inference.py's overlay_predictions for the frame: the uint8
+        [Hf, Wf, 3] blended frame on the GPU (a static buffer) and {'cars': n}."""
+        if self.overlay is None:
+            raise RuntimeError("annotate() needs Predictor(..., overlay=True)")
+        self(frame)
+        return self.overlay.result, self.overlay.detected_objects()
 
     def logits(self) -> torch.Tensor:
         """[1, C, H, W] logits of the last frame (the model's return value, src/unet.py:49)."""
