@@ -376,6 +376,16 @@ int seg_ce_upsample_grad(const float* low, long ld, int N, int H, int W, int C,
                          const long long* labels, int Ho, int Wo, int ignore_index,
                          const float* grad_out, const float* stats, float* dhigh, long ldh,
                          hipStream_t stream);
+/* Validation (the reference's disabled block, src/train.py:46-76, plus the metrics a
+ * segmenter reports): seg_ce_upsample_loss -- out3 is bitwise what it returns -- and, in
+ * the same pass, confusion[label * C + argmax] += 1 for every pixel whose label is neither
+ * ignore_index nor outside [0, C).  The argmax runs over the C real classes of the
+ * recomputed full-resolution logits; ties go to the lowest class (torch.max).
+ * `confusion`: C*C int64 in device memory, ADDED to (zero it once per epoch); NULL is
+ * hipErrorInvalidValue.  `work` >= seg_ce_workspace_floats(N*Ho*Wo). */
+int seg_ce_upsample_eval(const float* low, long ld, int N, int H, int W, int C,
+                         const long long* labels, int Ho, int Wo, int ignore_index,
+                         float* work, float* out3, long long* confusion, hipStream_t stream);
 
 /* ---- inference (inference.py: preprocess_image :28-46, model.eval() forward
  *      :23-25,162-163, overlay_predictions' argmax + resize :64-70) ---------- */
@@ -472,6 +482,8 @@ int seg_conv_igemm_bf16io(const seg_bf16* in, long ldin, int N, int H, int W, in
     add, long ldadd, float* stat, hipStream_t stream);
 int seg_ce_upsample_loss_bf16io(const seg_bf16* low, long ld, int N, int H, int W, int C, const long long* labels, int
     Ho, int Wo, int ignore_index, float* work, float* out2, hipStream_t stream);
+int seg_ce_upsample_eval_bf16io(const seg_bf16* low, long ld, int N, int H, int W, int C, const long long* labels, int
+    Ho, int Wo, int ignore_index, float* work, float* out3, long long* confusion, hipStream_t stream);
 int seg_ce_upsample_grad_bf16io(const seg_bf16* low, long ld, int N, int H, int W, int C, const long long* labels, int
     Ho, int Wo, int ignore_index, const float* grad_out, const float* stats, seg_bf16* dhigh, long ldh, hipStream_t
     stream);

@@ -76,12 +76,23 @@ __device__ __forceinline__ void softmax_stats(float (&z)[CP], int C, int y, floa
   }
 }
 
-template <int CP, typename T>
+// EVAL: the validation form (seg_ce_upsample_eval).  On top of the loss partials -- same grid,
+// same order, so out3 is bitwise the loss kernel's -- each valid pixel's argmax over the C real
+// classes (strict >, ascending: ties go to the lowest index, torch.max's rule) is binned into a
+// per-block LDS histogram [label][prediction]; its non-zero bins are then added to `confusion`
+// with 64-bit integer atomics (integer sums do not depend on arrival order: deterministic).
+template <int CP, typename T, bool EVAL>
 __global__ __launch_bounds__(256) void ce_up_loss_kernel(const T* __restrict__ low, long ld, int N, int H, int W,
                                                          int C, const long long* __restrict__ labels, int Ho, int Wo,
                                                          float sh, float sw, int ignore_index,
-                                                         float* __restrict__ part) {
+                                                         float* __restrict__ part,
+                                                         unsigned long long* __restrict__ confusion) {
   __shared__ float red_l[4], red_c[4], red_b[4];
+  __shared__ int hist[EVAL ? CMAX * CMAX : 1];
+  if constexpr (EVAL) {
+    for (int i = threadIdx.x; i < C * C; i += blockDim.x) hist[i] = 0;
+    __syncthreads();
+  }
   const long total = (long)N * Ho * Wo;
   float lsum = 0.f, cnt = 0.f, bad = 0.f;
   for (long p = blockIdx.x * (long)blockDim.x + threadIdx.x; p < total; p += (long)gridDim.x * blockDim.x) {
@@ -100,6 +111,17 @@ __global__ __launch_bounds__(256) void ce_up_loss_kernel(const T* __restrict__ l
     softmax_stats<CP>(z, C, (int)y, m, se, zy, false);
     lsum += m + logf(se) - zy;
     cnt += 1.f;
+    if constexpr (EVAL) {
+      int pred = 0;
+      float best = z[0];
+#pragma unroll
+      for (int c = 1; c < CP; ++c)
+        if (c < C && z[c] > best) {  // the padded lanes C..CP-1 never compete
+          best = z[c];
+          pred = c;
+        }
+      atomicAdd(&hist[(int)y * C + pred], 1);
+    }
   }
   lsum = wave_sum(lsum);
   cnt = wave_sum(cnt);
@@ -111,6 +133,12 @@ __global__ __launch_bounds__(256) void ce_up_loss_kernel(const T* __restrict__ l
     part[3 * blockIdx.x] = red_l[0] + red_l[1] + red_l[2] + red_l[3];
     part[3 * blockIdx.x + 1] = red_c[0] + red_c[1] + red_c[2] + red_c[3];
     part[3 * blockIdx.x + 2] = red_b[0] + red_b[1] + red_b[2] + red_b[3];
+  }
+  if constexpr (EVAL) {  // the __syncthreads above also closed the histogram
+    for (int i = threadIdx.x; i < C * C; i += blockDim.x) {
+      const int v = hist[i];
+      if (v) atomicAdd(confusion + i, (unsigned long long)v);
+    }
   }
 }
 
@@ -180,18 +208,20 @@ SEG_API long seg_ce_workspace_floats(long pixels) { return 3L * loss_blocks(pixe
 
 // Mean CE of bilinear_ac_true_x(Ho,Wo)(low) against labels.  out3[0] = loss,
 // out3[1] = number of non-ignored pixels, out3[2] = number of out-of-range labels.  `work` >= seg_ce_workspace_floats(N*Ho*Wo).
-template <typename T>
+// EVAL: also add each valid pixel to confusion[label][argmax] (C*C int64, device memory).
+template <typename T, bool EVAL = false>
 static int ce_loss_impl(const T* low, long ld, int N, int H, int W, int C, const long long* labels, int Ho, int Wo,
-                        int ignore_index, float* work, float* out2, hipStream_t stream) {
-  if ((ld & 3) || C > CMAX || C < 1) return (int)hipErrorInvalidValue;
+                        int ignore_index, float* work, float* out2, hipStream_t stream,
+                        long long* confusion = nullptr) {
+  if ((ld & 3) || C > CMAX || C < 1 || (EVAL && !confusion)) return (int)hipErrorInvalidValue;
   const long total = (long)N * Ho * Wo;
   const int nb = loss_blocks(total);
   const float sh = Ho > 1 ? (float)(H - 1) / (float)(Ho - 1) : 0.f;
   const float sw = Wo > 1 ? (float)(W - 1) / (float)(Wo - 1) : 0.f;
 #define SEG_CE_L(CP)                                                                                          \
   case CP:                                                                                                    \
-    hipLaunchKernelGGL((ce_up_loss_kernel<CP, T>), dim3(nb), dim3(256), 0, stream, low, ld, N, H, W, C, labels, Ho, \
-                       Wo, sh, sw, ignore_index, work);                                                      \
+    hipLaunchKernelGGL((ce_up_loss_kernel<CP, T, EVAL>), dim3(nb), dim3(256), 0, stream, low, ld, N, H, W, C,   \
+                       labels, Ho, Wo, sh, sw, ignore_index, work, (unsigned long long*)confusion);          \
     break
   switch ((C + 3) & ~3) {
     SEG_CE_L(4); SEG_CE_L(8); SEG_CE_L(12); SEG_CE_L(16); SEG_CE_L(20); SEG_CE_L(24); SEG_CE_L(28); SEG_CE_L(32);
@@ -208,6 +238,19 @@ SEG_API int seg_ce_upsample_loss_bf16io(const __bf16* low, long ld, int N, int H
                                         const long long* labels, int Ho, int Wo, int ignore_index, float* work,
                                         float* out2, hipStream_t stream) {
   return ce_loss_impl(low, ld, N, H, W, C, labels, Ho, Wo, ignore_index, work, out2, stream);
+}
+
+// Validation: seg_ce_upsample_loss (out3 bitwise the same) plus the confusion matrix of the
+// full-resolution argmax, confusion[label * C + prediction] += 1 per non-ignored in-range pixel.
+SEG_API int seg_ce_upsample_eval(const float* low, long ld, int N, int H, int W, int C, const long long* labels, int Ho,
+                                 int Wo, int ignore_index, float* work, float* out3, long long* confusion,
+                                 hipStream_t stream) {
+  return ce_loss_impl<float, true>(low, ld, N, H, W, C, labels, Ho, Wo, ignore_index, work, out3, stream, confusion);
+}
+SEG_API int seg_ce_upsample_eval_bf16io(const __bf16* low, long ld, int N, int H, int W, int C,
+                                        const long long* labels, int Ho, int Wo, int ignore_index, float* work,
+                                        float* out3, long long* confusion, hipStream_t stream) {
+  return ce_loss_impl<__bf16, true>(low, ld, N, H, W, C, labels, Ho, Wo, ignore_index, work, out3, stream, confusion);
 }
 
 // Full-resolution logit gradient (NHWC, ldh >= round4(C)); follow with

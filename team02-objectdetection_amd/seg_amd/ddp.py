@@ -325,6 +325,11 @@ class DataParallel(nn.Module):
         self._pre(x)
         return self.module.forward_loss(x, target, ignore_index)
 
+    def forward_metrics(self, x, target, confusion, ignore_index: int = -100):
+        """Validation step of this rank's shard: no gradients, so no bucket is armed and nothing is
+        broadcast; seg_amd.validate sums the ranks' matrices and losses with its own all-reduces."""
+        return self.module.forward_metrics(x, target, confusion, ignore_index)
+
     def state_dict(self, *args, **kwargs):
         return self.module.state_dict(*args, **kwargs)
 

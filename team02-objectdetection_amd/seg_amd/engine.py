@@ -1576,15 +1576,21 @@ def _check_input(x: torch.Tensor):
         raise NotImplementedError("gradient w.r.t. the input image is not supported")
 
 
-def _loss_forward(run, t, ignore_index):
-    """Fused final upsample + CrossEntropy over the run's low-res logits: stats = [loss, count, #bad labels]."""
+def _loss_forward(run, t, ignore_index, confusion=None):
+    """Fused final upsample + CrossEntropy over the run's low-res logits: stats = [loss, count, #bad labels].
+    confusion (int64 [C, C], "metrics" mode): the same pass also adds every valid pixel to
+    confusion[label, argmax] (seg_ce_upsample_eval)."""
     prog, lo, s = run.prog, run.prog.logits, run.stream
     N = prog.N
     Ho, Wo = prog.out_hw
     stats = run.tmp(3)  # loss, #valid, #out-of-range labels
     work = run.tmp(query("seg_ce_workspace_floats", N * Ho * Wo))
-    run.call(run.k("seg_ce_upsample_loss"), run.ptr(lo), lo.ld, N, lo.H, lo.W, lo.C, t.data_ptr(), Ho, Wo,
-             ignore_index, work.data_ptr(), stats.data_ptr(), s)
+    if confusion is None:
+        run.call(run.k("seg_ce_upsample_loss"), run.ptr(lo), lo.ld, N, lo.H, lo.W, lo.C, t.data_ptr(), Ho, Wo,
+                 ignore_index, work.data_ptr(), stats.data_ptr(), s)
+    else:
+        run.call(run.k("seg_ce_upsample_eval"), run.ptr(lo), lo.ld, N, lo.H, lo.W, lo.C, t.data_ptr(), Ho, Wo,
+                 ignore_index, work.data_ptr(), stats.data_ptr(), confusion.data_ptr(), s)
     run.target, run.stats = t, stats
     return stats
 
@@ -1606,7 +1612,8 @@ def _loss_backward(run, g, ignore_index):
 
 class Plan:
     """One (input shape, mode) of a model compiled to two launch tapes (seg_amd/tape.py):
-    the forward (weight repack, NCHW -> NHWC, every op, the fused loss or the NCHW logits)
+    the forward (weight repack, NCHW -> NHWC, every op, the fused loss or the NCHW logits;
+    mode "metrics": the fused loss + confusion matrix of validation, and no backward tape)
     and the backward (loss / logits gradient, every op in reverse, parameter gradients on
     the side stream, DataParallel bucket all-reduces at host-callback stops).  Recorded
     by the first step -- a normal program walk with every launch captured instead of
@@ -1644,7 +1651,7 @@ class Plan:
             tape.time(TIMER.kinds, TIMER.max_replays)
             TIMER.tapes.append(tape)
 
-    def forward(self, x, t):
+    def forward(self, x, t, confusion=None):
         from .tape import Recorder
         main, side = self._streams()
         N, _, H, W = x.shape
@@ -1659,6 +1666,8 @@ class Plan:
                 rec.external("t", t.data_ptr())
             if out is not None:
                 rec.external("out", out.data_ptr())
+            if confusion is not None:
+                rec.external("confusion", confusion.data_ptr())
             run = Run(self.prog, x, self.training, rec=rec, side=self.side)
             run.sync = self.sync
             if self.needs_grad:
@@ -1674,13 +1683,14 @@ class Plan:
                 run.call(run.k("seg_upsample_to_nchw"), run.ptr(lo), lo.ld, N, lo.H, lo.W, lo.C, out.data_ptr(), Ho,
                          Wo, 1, run.stream)
             else:
-                _loss_forward(run, t, self.ignore_index)
+                _loss_forward(run, t, self.ignore_index, confusion)
             run.rec = None
             self.run, self.fwd = run, rec.build()
         self._arm_timer(self.fwd)
         self.t = t  # the backward tape reads the labels: keep them alive until then
         self.fwd.bind(x=x.data_ptr(), t=t.data_ptr() if t is not None else 0,
-                      out=out.data_ptr() if out is not None else 0)
+                      out=out.data_ptr() if out is not None else 0,
+                      confusion=confusion.data_ptr() if confusion is not None else 0)
         self.fwd.run(main, side)
         if DEBUG_KEEP_RUN:
             global LAST_RUN
@@ -1775,6 +1785,25 @@ def _plan(model, prog, mode, ignore_index, sync, needs_grad, device):
     return plan
 
 
+def _publish_stats(model, stats):
+    """A fused loss has run: remember its stats buffer for bad_label_count / check_targets, start
+    the host copy of the out-of-range label count, and return the loss as a tensor of its own."""
+    model.__dict__["_segamd_last_stats"] = stats
+    out = stats[0].clone()  # the stats buffer is rewritten by the next step
+    # the out-of-range label count, copied to the host as soon as the loss kernel has run:
+    # train_one_epoch reads it before optimizer.step() without waiting for the backward
+    # (on the stats tensor's device and stream: the model need not be on the current device, ADVICE r4)
+    dev = stats.device
+    host = model.__dict__.get("_segamd_bad_host")
+    if host is None or host[2] != dev:
+        host = (torch.zeros(1, dtype=torch.float32).pin_memory(), torch.cuda.Event(), dev)
+        model.__dict__["_segamd_bad_host"] = host
+    with torch.cuda.device(dev):
+        host[0].copy_(stats[2:3], non_blocking=True)
+        host[1].record(torch.cuda.current_stream(dev))
+    return out
+
+
 class _SegFunction(torch.autograd.Function):
     """Whole-network forward/backward as one autograd node (replaying the plan's tapes)."""
 
@@ -1793,19 +1822,7 @@ class _SegFunction(torch.autograd.Function):
         plan = _plan(model, prog, mode, ignore_index, sync, needs_grad, x.device)
         out = plan.forward(x, t)
         if mode == "loss":
-            model.__dict__["_segamd_last_stats"] = plan.run.stats
-            out = plan.run.stats[0].clone()  # the stats buffer is rewritten by the next step
-            # the out-of-range label count, copied to the host as soon as the loss kernel has run:
-            # train_one_epoch reads it before optimizer.step() without waiting for the backward
-            # (on the stats tensor's device and stream: the model need not be on the current device)
-            dev = plan.run.stats.device
-            host = model.__dict__.get("_segamd_bad_host")
-            if host is None or host[2] != dev:
-                host = (torch.zeros(1, dtype=torch.float32).pin_memory(), torch.cuda.Event(), dev)
-                model.__dict__["_segamd_bad_host"] = host
-            with torch.cuda.device(dev):
-                host[0].copy_(plan.run.stats[2:3], non_blocking=True)
-                host[1].record(torch.cuda.current_stream(dev))
+            out = _publish_stats(model, plan.run.stats)
         else:  # an unfused criterion checks its own labels: no stale flag from an earlier fused loss
             model.__dict__.pop("_segamd_last_stats", None)
             model.__dict__.pop("_segamd_bad_host", None)
@@ -1903,3 +1920,30 @@ def run_loss(model, x: torch.Tensor, target: torch.Tensor, ignore_index: int = I
     _check_input(x)
     sync = model.__dict__.get("_segamd_sync")
     return _SegFunction.apply(model, "loss", x, target, ignore_index, sync, *_params_for(model, x))
+
+
+@torch.no_grad()
+def run_metrics(model, x: torch.Tensor, target: torch.Tensor, confusion: torch.Tensor,
+                ignore_index: int = IGNORE_INDEX) -> torch.Tensor:
+    """Validation forward: the fused loss of run_loss, and in the same kernel
+    confusion[label, argmax of the full-resolution logits] += 1 for every valid pixel
+    (csrc/loss.hip: seg_ce_upsample_eval).  A forward tape only: no gradient is ever built, so
+    DataParallel's buckets are not involved (sync is None).  Plans are keyed by model.training
+    like the others: eval() uses the running statistics, train() the batch's."""
+    _check_input(x)
+    x = x.contiguous()
+    N, _, H, W = x.shape
+    prog = get_program(model, N, H, W)
+    Ho, Wo = prog.out_hw
+    C = prog.logits.C
+    t = target.contiguous()
+    if t.dtype != torch.int64 or tuple(t.shape) != (N, Ho, Wo) or t.device != x.device:
+        raise ValueError(f"target must be int64 [{N},{Ho},{Wo}] on {x.device}, got {tuple(t.shape)} {t.dtype} "
+                         f"on {t.device}")
+    if (confusion.dtype != torch.int64 or tuple(confusion.shape) != (C, C) or confusion.device != x.device
+            or not confusion.is_contiguous()):
+        raise ValueError(f"confusion must be a contiguous int64 [{C},{C}] tensor on {x.device}, got "
+                         f"{tuple(confusion.shape)} {confusion.dtype} on {confusion.device}")
+    plan = _plan(model, prog, "metrics", ignore_index, None, False, x.device)
+    plan.forward(x, t, confusion)
+    return _publish_stats(model, plan.run.stats)

@@ -94,6 +94,10 @@ class TorchMobileNetV2UNet(MobileNetV2UNet):
     def forward_loss(self, x, target, ignore_index: int = -100):
         return nn.functional.cross_entropy(self(x), target, ignore_index=ignore_index)
 
+    def forward_metrics(self, x, target, confusion, ignore_index: int = -100):
+        from .unet import _torch_metrics
+        return _torch_metrics(self, x, target, confusion, ignore_index)
+
 
 class _TorchUNetMixin:
     def forward(self, x):
@@ -101,6 +105,10 @@ class _TorchUNetMixin:
 
     def forward_loss(self, x, target, ignore_index: int = -100):
         return nn.functional.cross_entropy(self(x), target, ignore_index=ignore_index)
+
+    def forward_metrics(self, x, target, confusion, ignore_index: int = -100):
+        from .unet import _torch_metrics
+        return _torch_metrics(self, x, target, confusion, ignore_index)
 
 
 class TorchUNet(_TorchUNetMixin, UNet):

@@ -1,0 +1,42 @@
+"""Segmentation metrics from a confusion matrix (row = label, column = predicted class).
+
+The reference has no metric code (its validation block, src/train.py:46-76, is commented
+out); the definitions are the ones seg_amd.detinit.miou fixes: IoU_c = TP / (TP + FP + FN),
+mIoU = the mean over the classes whose union is not empty.
+
+On the MI355X the matrix is filled by the fused validation kernel
+(`model.forward_metrics`, csrc/loss.hip: seg_ce_upsample_eval) and stays on the device for
+a whole pass; `summarize` is the one place it comes to the host.
+"""
+from __future__ import annotations
+
+import torch
+
+
+def add_confusion(confusion: torch.Tensor, pred: torch.Tensor, target: torch.Tensor, ignore_index: int = -100) -> None:
+    """confusion[label, pred] += 1 (in place, on confusion's device) for every pixel whose label is
+    neither ignore_index nor outside [0, C) -- the torch composition of what the fused kernel
+    counts, for CPU tensors and for criteria or models the fused path does not cover."""
+    C = confusion.shape[0]
+    t = target.reshape(-1)
+    p = pred.reshape(-1)
+    keep = (t != ignore_index) & (t >= 0) & (t < C)
+    idx = t[keep] * C + p[keep]
+    confusion += torch.bincount(idx, minlength=C * C).reshape(C, C).to(confusion.dtype)
+
+
+def summarize(confusion: torch.Tensor) -> dict:
+    """{"confusion": int64 CPU [C, C], "pixel_acc": float, "iou": float64 CPU [C] (NaN where the
+    class's union is empty), "miou": float (mean over the non-empty unions; NaN if there is none)}."""
+    cm = confusion.detach().to("cpu", torch.int64)
+    d = cm.double()
+    tp = d.diag()
+    union = d.sum(0) + d.sum(1) - tp
+    valid = union > 0
+    iou = torch.full_like(tp, float("nan"))
+    iou[valid] = tp[valid] / union[valid]
+    total = d.sum()
+    return {"confusion": cm,
+            "pixel_acc": float(tp.sum() / total) if total > 0 else float("nan"),
+            "iou": iou,
+            "miou": float(iou[valid].mean()) if valid.any() else float("nan")}

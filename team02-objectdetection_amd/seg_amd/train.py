@@ -144,23 +144,117 @@ def train_one_epoch(model, train_loader, criterion, optimizer, device, epoch: in
     return train_loss / max(n, 1)
 
 
+def _num_classes(core) -> int:
+    """Output channels of a segmentation model: its last convolution's (outc / sem_out heads)."""
+    convs = [m for m in core.modules() if isinstance(m, nn.Conv2d)]
+    if not convs:
+        raise ValueError("validate(): cannot tell the number of classes of a model without convolutions")
+    return convs[-1].out_channels
+
+
+def validate(model, val_loader, criterion, device, progress: bool = True, epoch: int = 0, epochs: int = 1) -> dict:
+    """One pass over `val_loader` in eval mode, without gradients: the reference's disabled
+    validation phase (src/train.py:46-66) plus the metrics of seg_amd.metrics.summarize.
+
+    Returns {"loss": mean of the batch means (val_loss += loss.item(); / len(val_loader)),
+    "confusion", "pixel_acc", "iou", "miou"}.  The previous train/eval mode is restored.
+
+    When `criterion` is a plain nn.CrossEntropyLoss() and the model has `forward_metrics`, each
+    batch is one fused forward (loss + argmax + confusion matrix from the low-resolution
+    logits); any other pair runs criterion(model(x), t) with argmax and bincount on the
+    device.  Either way the batch losses and the matrix stay on the device and the host waits
+    once, at the end of the pass -- so the bar shows no per-batch loss.  An out-of-range label
+    raises IndexError there.  Under torch.distributed every rank evaluates its own shard; the
+    matrices and [sum of batch losses, #batches, #bad labels] are summed with one all-reduce each
+    (on the wrapper's process group when the model has one) and every rank returns the same dict."""
+    from .metrics import add_confusion, summarize
+    core = getattr(model, "module", model)
+    ignore_index = getattr(criterion, "ignore_index", -100)
+    fused = hasattr(core, "forward_metrics") and _fusable_ce(criterion)
+    it = val_loader
+    if progress and tqdm is not None and _is_rank0():
+        it = tqdm(val_loader, desc=f"Epoch {epoch + 1}/{epochs} [Valid]", leave=True, position=0,
+                  bar_format="{l_bar}{bar:20}{r_bar}{bar:-20b}")
+    was_training = model.training
+    model.eval()
+    confusion = acc = None  # acc (float64): sum of batch losses, #batches, #out-of-range labels
+    try:
+        with torch.no_grad():
+            for inputs, targets in it:
+                inputs = inputs.to(device, non_blocking=True)
+                targets = targets.to(device, non_blocking=True)
+                if acc is None:
+                    acc = torch.zeros(3, dtype=torch.float64, device=inputs.device)
+                if fused:
+                    if confusion is None:
+                        C = _num_classes(core)
+                        confusion = torch.zeros((C, C), dtype=torch.int64, device=inputs.device)
+                    loss = model.forward_metrics(inputs, targets, confusion, ignore_index)
+                    if inputs.is_cuda:  # the CPU composition's F.cross_entropy raises by itself
+                        from .engine import bad_label_count
+                        acc[2] += bad_label_count(model)[0]
+                else:
+                    logits = model(inputs)
+                    loss = criterion(logits, targets)
+                    if confusion is None:
+                        C = logits.shape[1]
+                        confusion = torch.zeros((C, C), dtype=torch.int64, device=inputs.device)
+                    add_confusion(confusion, logits.argmax(1), targets, ignore_index)
+                acc[0] += loss.detach().double()
+                acc[1] += 1
+    finally:
+        model.train(was_training)
+    if acc is None:
+        raise ValueError("validate(): the validation loader yielded no batch")
+    if torch.distributed.is_available() and torch.distributed.is_initialized():
+        pg = getattr(model, "pg", None)
+        torch.distributed.all_reduce(confusion, group=pg)
+        torch.distributed.all_reduce(acc, group=pg)
+    # the pass's only host wait: one copy carries the matrix and the three float64 sums (as their bit patterns)
+    host = torch.cat([confusion.reshape(-1), acc.view(torch.int64)]).cpu()
+    loss_sum, nb, bad = host[-3:].view(torch.float64).tolist()
+    if bad:
+        raise IndexError(f"Target out of bounds: {int(bad)} label(s) outside [0, num_classes) that are not "
+                         "ignore_index (nn.CrossEntropyLoss raises on these)")
+    out = {"loss": loss_sum / nb}
+    out.update(summarize(host[:-3].reshape(confusion.shape)))
+    return out
+
+
 def train_model(model, train_loader, criterion, optimizer, device, epochs=10,
                 checkpoint_pattern: str | None = "Models/obj/obj_MOB_1_epoch_{epoch}.pth", progress: bool = True,
-                augment=None):
-    """Train for `epochs` epochs (src/train.py:6-79)."""
-    best_val_loss = float("inf")  # validation is disabled in the reference (src/train.py:46-76)
+                augment=None, val_loader=None, best_checkpoint: str | None = None):
+    """Train for `epochs` epochs (src/train.py:6-79).  With `val_loader`, each epoch ends with the
+    reference's validation phase (commented out there, src/train.py:46-76): validate(), the
+    epoch's result lines, and on an improved validation loss a state_dict at `best_checkpoint`
+    (when given).  Without it, output and files are the reference's as it stands."""
+    best_val_loss = float("inf")  # stays inf without a val_loader, as in the reference (src/train.py:46-76)
     for epoch in range(epochs):
         sampler = getattr(train_loader, "sampler", None)
         if hasattr(sampler, "set_epoch"):
             sampler.set_epoch(epoch)  # DistributedWeightedSampler: a new shared draw per epoch
         avg_train_loss = train_one_epoch(model, train_loader, criterion, optimizer, device, epoch, epochs, progress,
                                          augment)
+        val = None
+        if val_loader is not None:  # every rank: validate() all-reduces
+            val = validate(model, val_loader, criterion, device, progress, epoch, epochs)
         if _is_rank0():
+            if val is not None:
+                print(f"\nEpoch {epoch + 1}/{epochs}:")
             print(f"  Training Loss: {avg_train_loss:.4f}")
+            if val is not None:
+                print(f"  Validation Loss: {val['loss']:.4f}")
+                if val["loss"] < best_val_loss:
+                    print("  Validation loss improved! Saving model...")
+                    if best_checkpoint:
+                        os.makedirs(os.path.dirname(best_checkpoint) or ".", exist_ok=True)
+                        torch.save(getattr(model, "module", model).state_dict(), best_checkpoint)
             if checkpoint_pattern:
                 path = checkpoint_pattern.format(epoch=epoch + 1)
                 os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
                 core = getattr(model, "module", model)
                 torch.save(core.state_dict(), path)
+        if val is not None and val["loss"] < best_val_loss:  # every rank returns the same dict
+            best_val_loss = val["loss"]
     if _is_rank0():
         print(f"Training completed. Best validation loss: {best_val_loss:.4f}")

@@ -88,6 +88,27 @@ class _SegModel(nn.Module):
         from .engine import run_loss
         return run_loss(self, x, target, ignore_index)
 
+    def forward_metrics(self, x: torch.Tensor, target: torch.Tensor, confusion: torch.Tensor,
+                        ignore_index: int = -100) -> torch.Tensor:
+        """Validation step: returns nn.CrossEntropyLoss()(self(x), target) and adds every
+        non-ignored pixel to `confusion[label, argmax(self(x))]` (int64 [C, C] on x's device, in
+        place), without gradients.  On the MI355X one kernel does both from the low-resolution
+        logits: the full-resolution logits are never stored."""
+        if x.device.type == "cpu":
+            return _torch_metrics(self, x, target, confusion, ignore_index)
+        from .engine import run_metrics
+        return run_metrics(self, x, target, confusion, ignore_index)
+
+
+@torch.no_grad()
+def _torch_metrics(model, x, target, confusion, ignore_index):
+    """forward_metrics in torch ops (CPU tensors): F.cross_entropy raises on an out-of-range label by itself."""
+    from .metrics import add_confusion
+    logits = model(x)
+    loss = nn.functional.cross_entropy(logits, target, ignore_index=ignore_index)
+    add_confusion(confusion, logits.argmax(1), target, ignore_index)
+    return loss
+
 
 class MobileNetV2UNet(_SegModel):
     """src/unet.py:7-51.  `backbone_weights`: optional LOCAL path to torchvision
