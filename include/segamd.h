@@ -386,6 +386,38 @@ int seg_ce_upsample_grad(const float* low, long ld, int N, int H, int W, int C,
 int seg_ce_upsample_eval(const float* low, long ld, int N, int H, int W, int C,
                          const long long* labels, int Ho, int Wo, int ignore_index,
                          float* work, float* out3, long long* confusion, hipStream_t stream);
+/* nn.CrossEntropyLoss(weight=w, label_smoothing=eps, reduction="mean" | "sum") for class-index
+ * targets, fused with the same upsample: the weighted / smoothed forms of the three kernels
+ * above (same grid, same pixel -> thread mapping, the full-resolution logits never stored).
+ * Over the valid pixels V (label neither ignore_index nor outside [0, C)), with z_p the
+ * recomputed logits and lse_p = logsumexp(z_p):
+ *   nll = sum_p w[y_p] (lse_p - z_p[y_p]),  smooth = sum_p sum_c w[c] (lse_p - z_p[c]),
+ *   D = sum_p w[y_p] (mean) | 1 (sum),      loss = ((1 - eps) nll + (eps / C) smooth) / D,
+ *   dloss/dz_p[c] = g / D [(1 - eps) w[y_p] (softmax_c - [c == y_p]) + (eps / C) (softmax_c sum_k w[k] - w[c])].
+ * class_weight: C floats in device memory, or NULL (all ones).  reduction: 0 = mean, 1 = sum.
+ * out4 = [loss, D, #labels outside [0, C) that are not ignore_index, #valid pixels]: the first
+ * three slots are out2's, so a caller of the plain entry points reads them unchanged.  Mean
+ * reduction with D == 0 gives NaN (0/0, as aten); sum reduction over no valid pixel gives 0; an
+ * out-of-range label makes the loss and every gradient NaN.  With class_weight NULL or all
+ * ones, eps = 0 and reduction 0, out4[0..2] and dhigh are bitwise the plain entry points' (every
+ * rounding of csrc/loss.hip is written out, so all its kernels recompute the same logits).
+ * `stats` of _grad is the out4 of _loss / _eval; `work` >= seg_cew_workspace_floats(N*Ho*Wo).
+ * hipErrorInvalidValue before any launch: reduction not 0 / 1, label_smoothing outside [0, 1],
+ * C outside [1, 32], ld (ldh) % 4 != 0, or (_eval) confusion NULL. */
+long seg_cew_workspace_floats(long pixels);
+int seg_cew_upsample_loss(const float* low, long ld, int N, int H, int W, int C,
+                          const long long* labels, int Ho, int Wo, int ignore_index,
+                          const float* class_weight, float label_smoothing, int reduction,
+                          float* work, float* out4, hipStream_t stream);
+int seg_cew_upsample_grad(const float* low, long ld, int N, int H, int W, int C,
+                          const long long* labels, int Ho, int Wo, int ignore_index,
+                          const float* class_weight, float label_smoothing,
+                          const float* grad_out, const float* stats, float* dhigh, long ldh,
+                          hipStream_t stream);
+int seg_cew_upsample_eval(const float* low, long ld, int N, int H, int W, int C,
+                          const long long* labels, int Ho, int Wo, int ignore_index,
+                          const float* class_weight, float label_smoothing, int reduction,
+                          float* work, float* out4, long long* confusion, hipStream_t stream);
 
 /* ---- inference (inference.py: preprocess_image :28-46, model.eval() forward
  *      :23-25,162-163, overlay_predictions' argmax + resize :64-70) ---------- */
@@ -487,6 +519,15 @@ int seg_ce_upsample_eval_bf16io(const seg_bf16* low, long ld, int N, int H, int 
 int seg_ce_upsample_grad_bf16io(const seg_bf16* low, long ld, int N, int H, int W, int C, const long long* labels, int
     Ho, int Wo, int ignore_index, const float* grad_out, const float* stats, seg_bf16* dhigh, long ldh, hipStream_t
     stream);
+int seg_cew_upsample_loss_bf16io(const seg_bf16* low, long ld, int N, int H, int W, int C, const long long* labels, int
+    Ho, int Wo, int ignore_index, const float* class_weight, float label_smoothing, int reduction, float* work, float*
+    out4, hipStream_t stream);
+int seg_cew_upsample_eval_bf16io(const seg_bf16* low, long ld, int N, int H, int W, int C, const long long* labels, int
+    Ho, int Wo, int ignore_index, const float* class_weight, float label_smoothing, int reduction, float* work, float*
+    out4, long long* confusion, hipStream_t stream);
+int seg_cew_upsample_grad_bf16io(const seg_bf16* low, long ld, int N, int H, int W, int C, const long long* labels, int
+    Ho, int Wo, int ignore_index, const float* class_weight, float label_smoothing, const float* grad_out, const float*
+    stats, seg_bf16* dhigh, long ldh, hipStream_t stream);
 int seg_upsample_fwd_bf16io(const seg_bf16* in, long ldin, int N, int H, int W, int C, seg_bf16* out, long ldout, int
     Ho, int Wo, int ac, hipStream_t stream);
 int seg_upsample_bwd_bf16io(const void* dout, long ldout, int nchw_grad, int N, int Ho, int Wo, int C, seg_bf16* din,

@@ -14,7 +14,27 @@
 // bounds") is counted in out2[2] and poisons the loss and the gradient with NaN --
 // stream-ordered, no host sync; the host raises when it reads the loss
 // (seg_amd.train / engine.check_targets).
+//
+// The seg_cew_* entry points are the same kernels with aten's remaining options for
+// class-index targets (the instantiations that take a CeOpt): class weights w (all ones when NULL),
+// label smoothing eps and reduction mean / sum.  Over the valid pixels V,
+//   nll    = sum_p w[y_p] * (lse_p - z_p[y_p]),   smooth = sum_p sum_c w[c] * (lse_p - z_p[c]),
+//   D      = sum_p w[y_p] (mean) | 1 (sum),       loss   = ((1 - eps) * nll + (eps / C) * smooth) / D,
+//   d loss / d z_p[c] = (g / D) * [(1 - eps) * w[y_p] * (softmax_c - [c == y_p])
+//                                  + (eps / C) * (softmax_c * sum_k w[k] - w[c])].
+// Same grid, same pixel -> thread mapping and the same per-pixel expressions as the plain
+// kernels: with w = 1 (or NULL), eps = 0 and mean reduction every term is the plain kernel's
+// expression times 1 plus 0, so loss, D and gradient are bitwise the plain entry points'.
 #include "common.h"
+
+// Every rounding in this file is written out: no implicit contraction of a * b + c into an fma,
+// and __builtin_fmaf where one is meant.  Left to the compiler, the same source expression (the
+// bilinear blend above all) was contracted differently from one instantiation to the next, so
+// the loss, eval and gradient kernels, their bf16 twins and the weighted forms recomputed logits
+// that differed in the last bit.  Now they all recompute the same numbers, and what the header
+// promises bit for bit (eval = loss, bf16 = fp32 rounded once, no options = plain) holds by
+// construction.  The forms chosen are the ones the fp32 gradient kernels always compiled to.
+#pragma clang fp contract(off)
 
 namespace {
 
@@ -30,7 +50,7 @@ __device__ __forceinline__ LinAC lin_ac(int dst, int in, float scale) {
   LinAC r;
   r.i0 = i0;
   r.i1 = i0 + (i0 < in - 1 ? 1 : 0);
-  r.l1 = fminf(fmaxf(src - (float)i0, 0.f), 1.f);
+  r.l1 = fminf(fmaxf(__builtin_fmaf(scale, (float)dst, -(float)i0), 0.f), 1.f);
   r.l0 = 1.f - r.l1;
   return r;
 }
@@ -50,10 +70,13 @@ __device__ __forceinline__ void full_res_logits(const T* __restrict__ low, long 
   const T* p11 = base + ((long)lh.i1 * W + lw.i1) * ld;
 #pragma unroll
   for (int c = 0; c < CP; c += 4) {
-    const f32x4 o = lh.l0 * (lw.l0 * ld4(p00 + c) + lw.l1 * ld4(p01 + c)) +
-                    lh.l1 * (lw.l0 * ld4(p10 + c) + lw.l1 * ld4(p11 + c));
+    const f32x4 v00 = ld4(p00 + c), v01 = ld4(p01 + c), v10 = ld4(p10 + c), v11 = ld4(p11 + c);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) z[c + j] = o[j];
+    for (int j = 0; j < 4; ++j) {  // lh.l0 * (lw.l0 * v00 + lw.l1 * v01) + lh.l1 * (lw.l0 * v10 + lw.l1 * v11)
+      const float top = __builtin_fmaf(v01[j], lw.l1, v00[j] * lw.l0);
+      const float bot = __builtin_fmaf(v11[j], lw.l1, v10[j] * lw.l0);
+      z[c + j] = lh.l0 * top + lh.l1 * bot;
+    }
   }
 }
 
@@ -76,25 +99,57 @@ __device__ __forceinline__ void softmax_stats(float (&z)[CP], int C, int y, floa
   }
 }
 
+// The class weights as CP wave-uniform values (scalar loads; 1 when cw is NULL, 0 on the padded
+// lanes) and their sum over the C real classes, in ascending order.
+template <int CP>
+__device__ __forceinline__ float class_weights(const float* __restrict__ cw, int C, float (&w)[CP]) {
+  float sw = 0.f;
+#pragma unroll
+  for (int c = 0; c < CP; ++c) {
+    w[c] = c < C ? (cw ? cw[c] : 1.f) : 0.f;
+    sw += w[c];
+  }
+  return sw;
+}
+
+// The options of the weighted / smoothed form.  The kernels take them as a trailing parameter pack
+// that is empty for the plain entry points, whose instantiations therefore keep their parameters
+// and compile none of the option code.
+struct CeOpt {
+  const float* cw;  // C class weights in device memory, or NULL = all ones
+  float eps;        // label smoothing
+  int reduction;    // 0 = mean, 1 = sum (read by the finalize only)
+};
+__device__ __forceinline__ CeOpt ce_opt() { return CeOpt{nullptr, 0.f, 0}; }
+__device__ __forceinline__ CeOpt ce_opt(CeOpt o) { return o; }
+
 // EVAL: the validation form (seg_ce_upsample_eval).  On top of the loss partials -- same grid,
 // same order, so out3 is bitwise the loss kernel's -- each valid pixel's argmax over the C real
 // classes (strict >, ascending: ties go to the lowest index, torch.max's rule) is binned into a
 // per-block LDS histogram [label][prediction]; its non-zero bins are then added to `confusion`
 // with 64-bit integer atomics (integer sums do not depend on arrival order: deterministic).
-template <int CP, typename T, bool EVAL>
+// O = CeOpt: the weighted / smoothed form (seg_cew_*).  Five partials per block instead of three:
+// [nll, sum of w[y], #out-of-range, smooth, #valid].
+template <int CP, typename T, bool EVAL, typename... O>
 __global__ __launch_bounds__(256) void ce_up_loss_kernel(const T* __restrict__ low, long ld, int N, int H, int W,
                                                          int C, const long long* __restrict__ labels, int Ho, int Wo,
                                                          float sh, float sw, int ignore_index,
                                                          float* __restrict__ part,
-                                                         unsigned long long* __restrict__ confusion) {
+                                                         unsigned long long* __restrict__ confusion, O... opt) {
+  constexpr bool WS = sizeof...(O) > 0;
+  constexpr int NP = WS ? 5 : 3;
   __shared__ float red_l[4], red_c[4], red_b[4];
+  __shared__ float red_s[WS ? 4 : 1], red_v[WS ? 4 : 1];
   __shared__ int hist[EVAL ? CMAX * CMAX : 1];
   if constexpr (EVAL) {
     for (int i = threadIdx.x; i < C * C; i += blockDim.x) hist[i] = 0;
     __syncthreads();
   }
   const long total = (long)N * Ho * Wo;
-  float lsum = 0.f, cnt = 0.f, bad = 0.f;
+  float lsum = 0.f, cnt = 0.f, bad = 0.f, ssum = 0.f, val = 0.f;
+  float w[WS ? CP : 1];
+  float wsum = 0.f;
+  if constexpr (WS) wsum = class_weights<CP>(ce_opt(opt...).cw, C, w);
   for (long p = blockIdx.x * (long)blockDim.x + threadIdx.x; p < total; p += (long)gridDim.x * blockDim.x) {
     const long long y = labels[p];
     if (y == ignore_index) continue;
@@ -109,8 +164,23 @@ __global__ __launch_bounds__(256) void ce_up_loss_kernel(const T* __restrict__ l
     full_res_logits<CP, T>(low, ld, H, W, n, r, s, sh, sw, z);
     float m, se, zy;
     softmax_stats<CP>(z, C, (int)y, m, se, zy, false);
-    lsum += m + logf(se) - zy;
-    cnt += 1.f;
+    if constexpr (WS) {
+      // w[y] by the select that picks z[y]; sum_c w[c] * (z[c] - m) after the row maximum is gone
+      float wy = 0.f, wz = 0.f;
+#pragma unroll
+      for (int c = 0; c < CP; ++c) {
+        wy = c == (int)y ? w[c] : wy;
+        if (c < C) wz = __builtin_fmaf(w[c], z[c] - m, wz);  // the padded lanes may hold anything
+      }
+      const float lse = logf(se);
+      lsum = __builtin_fmaf(wy, m + lse - zy, lsum);  // wy = 1: the plain branch's sum
+      cnt += wy;
+      ssum += __builtin_fmaf(wsum, lse, -wz);
+      val += 1.f;
+    } else {
+      lsum += m + logf(se) - zy;
+      cnt += 1.f;
+    }
     if constexpr (EVAL) {
       int pred = 0;
       float best = z[0];
@@ -128,11 +198,20 @@ __global__ __launch_bounds__(256) void ce_up_loss_kernel(const T* __restrict__ l
   bad = wave_sum(bad);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   if (lane == 0) { red_l[wave] = lsum; red_c[wave] = cnt; red_b[wave] = bad; }
+  if constexpr (WS) {
+    ssum = wave_sum(ssum);
+    val = wave_sum(val);
+    if (lane == 0) { red_s[wave] = ssum; red_v[wave] = val; }
+  }
   __syncthreads();
   if (threadIdx.x == 0) {
-    part[3 * blockIdx.x] = red_l[0] + red_l[1] + red_l[2] + red_l[3];
-    part[3 * blockIdx.x + 1] = red_c[0] + red_c[1] + red_c[2] + red_c[3];
-    part[3 * blockIdx.x + 2] = red_b[0] + red_b[1] + red_b[2] + red_b[3];
+    part[NP * blockIdx.x] = red_l[0] + red_l[1] + red_l[2] + red_l[3];
+    part[NP * blockIdx.x + 1] = red_c[0] + red_c[1] + red_c[2] + red_c[3];
+    part[NP * blockIdx.x + 2] = red_b[0] + red_b[1] + red_b[2] + red_b[3];
+    if constexpr (WS) {
+      part[NP * blockIdx.x + 3] = red_s[0] + red_s[1] + red_s[2] + red_s[3];
+      part[NP * blockIdx.x + 4] = red_v[0] + red_v[1] + red_v[2] + red_v[3];
+    }
   }
   if constexpr (EVAL) {  // the __syncthreads above also closed the histogram
     for (int i = threadIdx.x; i < C * C; i += blockDim.x) {
@@ -162,15 +241,55 @@ __global__ void ce_finalize_kernel(const float* __restrict__ part, int nblk, flo
   }
 }
 
+// out4 = [loss, D, #out-of-range labels, #valid pixels] of the weighted / smoothed form; D = sum of
+// w[y] (mean; 0/0 = nan as aten when it is 0) or 1 (sum).  eps == 0 leaves the smoothing sum out, so
+// the loss is then the plain finalize's l / c.
+__global__ void cew_finalize_kernel(const float* __restrict__ part, int nblk, float eps, int C, int reduction,
+                                    float* out) {
+  double l = 0.0, c = 0.0, b = 0.0, sm = 0.0, v = 0.0;
+  for (int k = threadIdx.x; k < nblk; k += 64) {
+    l += part[5 * k];
+    c += part[5 * k + 1];
+    b += part[5 * k + 2];
+    sm += part[5 * k + 3];
+    v += part[5 * k + 4];
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    l += __shfl_xor(l, o, 64);
+    c += __shfl_xor(c, o, 64);
+    b += __shfl_xor(b, o, 64);
+    sm += __shfl_xor(sm, o, 64);
+    v += __shfl_xor(v, o, 64);
+  }
+  if (threadIdx.x == 0) {
+    const double d = reduction == 0 ? c : 1.0;
+    const double num = eps > 0.f ? (1.0 - (double)eps) * l + ((double)eps / C) * sm : l;
+    out[0] = b > 0.0 ? __builtin_nanf("") : (float)(num / d);
+    out[1] = (float)d;
+    out[2] = (float)b;
+    out[3] = (float)v;
+  }
+}
+
 // dhigh[p][c] = g * (softmax(z_p)[c] - [c == y_p]) / count, NHWC (ld >= round4(C)).
-template <int CP, typename T>
+// O = CeOpt: g / D * [(1 - eps) * w[y] * (softmax_c - [c == y]) + (eps / C) * (softmax_c * sum w - w[c])], D = stats[1].
+template <int CP, typename T, typename... O>
 __global__ __launch_bounds__(256) void ce_up_grad_kernel(const T* __restrict__ low, long ld, int N, int H, int W,
                                                          int C, const long long* __restrict__ labels, int Ho, int Wo,
                                                          float sh, float sw, int ignore_index,
                                                          const float* __restrict__ gout, const float* __restrict__ stats,
-                                                         T* __restrict__ dhigh, long ldh) {
+                                                         T* __restrict__ dhigh, long ldh, O... opt) {
+  constexpr bool WS = sizeof...(O) > 0;
   const long total = (long)N * Ho * Wo;
   const float scale = stats[2] > 0.f ? __builtin_nanf("") : gout[0] / stats[1];
+  float w[WS ? CP : 1];
+  float wsum = 0.f, keep = 1.f, spread = 0.f;
+  if constexpr (WS) {
+    const CeOpt o = ce_opt(opt...);
+    wsum = class_weights<CP>(o.cw, C, w);
+    keep = 1.f - o.eps;
+    spread = o.eps / (float)C;
+  }
   for (long p = blockIdx.x * (long)blockDim.x + threadIdx.x; p < total; p += (long)gridDim.x * blockDim.x) {
     const long long y = labels[p];
     T* d = dhigh + p * ldh;
@@ -187,13 +306,26 @@ __global__ __launch_bounds__(256) void ce_up_grad_kernel(const T* __restrict__ l
     float m, se, zy;
     softmax_stats<CP>(z, C, (int)y, m, se, zy, true);
     const float inv = 1.f / se;
+    float kw = 0.f;  // (1 - eps) * w[y]
+    if constexpr (WS) {
+#pragma unroll
+      for (int c = 0; c < CP; ++c) kw = c == (int)y ? w[c] : kw;
+      kw *= keep;
+    }
 #pragma unroll
     for (int c = 0; c < CP; c += 4) {
       f32x4 o;
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const int cc = c + j;
-        o[j] = cc < C ? scale * (z[cc] * inv - (cc == (int)y ? 1.f : 0.f)) : 0.f;
+        if constexpr (WS) {
+          // softmax - onehot as in the plain branch: with w = 1 and eps = 0 the rest is * 1 and + 0
+          const float nl = __builtin_fmaf(z[cc], inv, cc == (int)y ? -1.f : -0.f);
+          const float sm = __builtin_fmaf(z[cc] * inv, wsum, -w[cc]);
+          o[j] = cc < C ? scale * __builtin_fmaf(spread, sm, kw * nl) : 0.f;
+        } else {
+          o[j] = cc < C ? scale * __builtin_fmaf(z[cc], inv, cc == (int)y ? -1.f : -0.f) : 0.f;
+        }
       }
       st4(d + c, o);
     }
@@ -209,35 +341,45 @@ SEG_API long seg_ce_workspace_floats(long pixels) { return 3L * loss_blocks(pixe
 // Mean CE of bilinear_ac_true_x(Ho,Wo)(low) against labels.  out3[0] = loss,
 // out3[1] = number of non-ignored pixels, out3[2] = number of out-of-range labels.  `work` >= seg_ce_workspace_floats(N*Ho*Wo).
 // EVAL: also add each valid pixel to confusion[label][argmax] (C*C int64, device memory).
-template <typename T, bool EVAL = false>
+// opt (seg_cew_*): one CeOpt; out2 is then out4.
+inline bool ce_opt_ok() { return true; }
+inline bool ce_opt_ok(CeOpt o) { return (o.reduction == 0 || o.reduction == 1) && o.eps >= 0.f && o.eps <= 1.f; }
+
+template <typename T, bool EVAL = false, typename... O>
 static int ce_loss_impl(const T* low, long ld, int N, int H, int W, int C, const long long* labels, int Ho, int Wo,
-                        int ignore_index, float* work, float* out2, hipStream_t stream,
-                        long long* confusion = nullptr) {
-  if ((ld & 3) || C > CMAX || C < 1 || (EVAL && !confusion)) return (int)hipErrorInvalidValue;
+                        int ignore_index, float* work, float* out2, hipStream_t stream, long long* confusion,
+                        O... opt) {
+  constexpr bool WS = sizeof...(O) > 0;
+  if ((ld & 3) || C > CMAX || C < 1 || (EVAL && !confusion) || !ce_opt_ok(opt...)) return (int)hipErrorInvalidValue;
   const long total = (long)N * Ho * Wo;
   const int nb = loss_blocks(total);
   const float sh = Ho > 1 ? (float)(H - 1) / (float)(Ho - 1) : 0.f;
   const float sw = Wo > 1 ? (float)(W - 1) / (float)(Wo - 1) : 0.f;
 #define SEG_CE_L(CP)                                                                                          \
   case CP:                                                                                                    \
-    hipLaunchKernelGGL((ce_up_loss_kernel<CP, T, EVAL>), dim3(nb), dim3(256), 0, stream, low, ld, N, H, W, C,   \
-                       labels, Ho, Wo, sh, sw, ignore_index, work, (unsigned long long*)confusion);          \
+    hipLaunchKernelGGL((ce_up_loss_kernel<CP, T, EVAL, O...>), dim3(nb), dim3(256), 0, stream, low, ld, N, H,  \
+                       W, C, labels, Ho, Wo, sh, sw, ignore_index, work, (unsigned long long*)confusion,     \
+                       opt...);                                                                               \
     break
   switch ((C + 3) & ~3) {
     SEG_CE_L(4); SEG_CE_L(8); SEG_CE_L(12); SEG_CE_L(16); SEG_CE_L(20); SEG_CE_L(24); SEG_CE_L(28); SEG_CE_L(32);
   }
 #undef SEG_CE_L
-  hipLaunchKernelGGL(ce_finalize_kernel, dim3(1), dim3(64), 0, stream, work, nb, out2);
+  if constexpr (WS) {
+    const CeOpt o = CeOpt{opt...};
+    hipLaunchKernelGGL(cew_finalize_kernel, dim3(1), dim3(64), 0, stream, work, nb, o.eps, C, o.reduction, out2);
+  } else
+    hipLaunchKernelGGL(ce_finalize_kernel, dim3(1), dim3(64), 0, stream, work, nb, out2);
   SEG_RET_LAST();
 }
 SEG_API int seg_ce_upsample_loss(const float* low, long ld, int N, int H, int W, int C, const long long* labels, int Ho,
                                  int Wo, int ignore_index, float* work, float* out2, hipStream_t stream) {
-  return ce_loss_impl(low, ld, N, H, W, C, labels, Ho, Wo, ignore_index, work, out2, stream);
+  return ce_loss_impl(low, ld, N, H, W, C, labels, Ho, Wo, ignore_index, work, out2, stream, nullptr);
 }
 SEG_API int seg_ce_upsample_loss_bf16io(const __bf16* low, long ld, int N, int H, int W, int C,
                                         const long long* labels, int Ho, int Wo, int ignore_index, float* work,
                                         float* out2, hipStream_t stream) {
-  return ce_loss_impl(low, ld, N, H, W, C, labels, Ho, Wo, ignore_index, work, out2, stream);
+  return ce_loss_impl(low, ld, N, H, W, C, labels, Ho, Wo, ignore_index, work, out2, stream, nullptr);
 }
 
 // Validation: seg_ce_upsample_loss (out3 bitwise the same) plus the confusion matrix of the
@@ -255,19 +397,19 @@ SEG_API int seg_ce_upsample_eval_bf16io(const __bf16* low, long ld, int N, int H
 
 // Full-resolution logit gradient (NHWC, ldh >= round4(C)); follow with
 // seg_upsample_bwd(nchw_grad = 0, ac = 1) to reach the low-res logits.
-template <typename T>
+template <typename T, typename... O>
 static int ce_grad_impl(const T* low, long ld, int N, int H, int W, int C, const long long* labels, int Ho, int Wo,
                         int ignore_index, const float* grad_out, const float* stats, T* dhigh, long ldh,
-                        hipStream_t stream) {
-  if ((ld & 3) || (ldh & 3) || C > CMAX || C < 1) return (int)hipErrorInvalidValue;
+                        hipStream_t stream, O... opt) {
+  if ((ld & 3) || (ldh & 3) || C > CMAX || C < 1 || !ce_opt_ok(opt...)) return (int)hipErrorInvalidValue;
   const long total = (long)N * Ho * Wo;
   const float sh = Ho > 1 ? (float)(H - 1) / (float)(Ho - 1) : 0.f;
   const float sw = Wo > 1 ? (float)(W - 1) / (float)(Wo - 1) : 0.f;
   const int grid = (int)std::min<long>(seg_cdiv(total, 256), 8192);
 #define SEG_CE_G(CP)                                                                                            \
   case CP:                                                                                                      \
-    hipLaunchKernelGGL((ce_up_grad_kernel<CP, T>), dim3(grid), dim3(256), 0, stream, low, ld, N, H, W, C, labels, Ho, \
-                       Wo, sh, sw, ignore_index, grad_out, stats, dhigh, ldh);                                 \
+    hipLaunchKernelGGL((ce_up_grad_kernel<CP, T, O...>), dim3(grid), dim3(256), 0, stream, low, ld, N, H, W, C,  \
+                       labels, Ho, Wo, sh, sw, ignore_index, grad_out, stats, dhigh, ldh, opt...);             \
     break
   switch ((C + 3) & ~3) {
     SEG_CE_G(4); SEG_CE_G(8); SEG_CE_G(12); SEG_CE_G(16); SEG_CE_G(20); SEG_CE_G(24); SEG_CE_G(28); SEG_CE_G(32);
@@ -285,4 +427,49 @@ SEG_API int seg_ce_upsample_grad_bf16io(const __bf16* low, long ld, int N, int H
                                         const float* grad_out, const float* stats, __bf16* dhigh, long ldh,
                                         hipStream_t stream) {
   return ce_grad_impl(low, ld, N, H, W, C, labels, Ho, Wo, ignore_index, grad_out, stats, dhigh, ldh, stream);
+}
+
+// ---- class weights, label smoothing, reduction mean / sum (the header comment has the formulas) ----
+// out4 = [loss, D, #out-of-range labels, #valid pixels]; `work` >= seg_cew_workspace_floats(N*Ho*Wo).
+SEG_API long seg_cew_workspace_floats(long pixels) { return 5L * loss_blocks(pixels); }
+
+SEG_API int seg_cew_upsample_loss(const float* low, long ld, int N, int H, int W, int C, const long long* labels,
+                                  int Ho, int Wo, int ignore_index, const float* class_weight, float label_smoothing,
+                                  int reduction, float* work, float* out4, hipStream_t stream) {
+  return ce_loss_impl<float, false>(low, ld, N, H, W, C, labels, Ho, Wo, ignore_index, work, out4, stream, nullptr,
+                                    CeOpt{class_weight, label_smoothing, reduction});
+}
+SEG_API int seg_cew_upsample_loss_bf16io(const __bf16* low, long ld, int N, int H, int W, int C,
+                                         const long long* labels, int Ho, int Wo, int ignore_index,
+                                         const float* class_weight, float label_smoothing, int reduction, float* work,
+                                         float* out4, hipStream_t stream) {
+  return ce_loss_impl<__bf16, false>(low, ld, N, H, W, C, labels, Ho, Wo, ignore_index, work, out4, stream, nullptr,
+                                     CeOpt{class_weight, label_smoothing, reduction});
+}
+SEG_API int seg_cew_upsample_eval(const float* low, long ld, int N, int H, int W, int C, const long long* labels,
+                                  int Ho, int Wo, int ignore_index, const float* class_weight, float label_smoothing,
+                                  int reduction, float* work, float* out4, long long* confusion, hipStream_t stream) {
+  return ce_loss_impl<float, true>(low, ld, N, H, W, C, labels, Ho, Wo, ignore_index, work, out4, stream, confusion,
+                                   CeOpt{class_weight, label_smoothing, reduction});
+}
+SEG_API int seg_cew_upsample_eval_bf16io(const __bf16* low, long ld, int N, int H, int W, int C,
+                                         const long long* labels, int Ho, int Wo, int ignore_index,
+                                         const float* class_weight, float label_smoothing, int reduction, float* work,
+                                         float* out4, long long* confusion, hipStream_t stream) {
+  return ce_loss_impl<__bf16, true>(low, ld, N, H, W, C, labels, Ho, Wo, ignore_index, work, out4, stream, confusion,
+                                    CeOpt{class_weight, label_smoothing, reduction});
+}
+SEG_API int seg_cew_upsample_grad(const float* low, long ld, int N, int H, int W, int C, const long long* labels,
+                                  int Ho, int Wo, int ignore_index, const float* class_weight, float label_smoothing,
+                                  const float* grad_out, const float* stats, float* dhigh, long ldh,
+                                  hipStream_t stream) {
+  return ce_grad_impl(low, ld, N, H, W, C, labels, Ho, Wo, ignore_index, grad_out, stats, dhigh, ldh, stream,
+                      CeOpt{class_weight, label_smoothing, 0});
+}
+SEG_API int seg_cew_upsample_grad_bf16io(const __bf16* low, long ld, int N, int H, int W, int C,
+                                         const long long* labels, int Ho, int Wo, int ignore_index,
+                                         const float* class_weight, float label_smoothing, const float* grad_out,
+                                         const float* stats, __bf16* dhigh, long ldh, hipStream_t stream) {
+  return ce_grad_impl(low, ld, N, H, W, C, labels, Ho, Wo, ignore_index, grad_out, stats, dhigh, ldh, stream,
+                      CeOpt{class_weight, label_smoothing, 0});
 }

@@ -5,6 +5,7 @@ Public surface (drop-in for the reference's src/unet.py and src/train.py):
     MobileNetV2UNet, UNet, LightUNet, double_conv, inconv, down, up, outconv
     train_model, train_one_epoch
     validate, summarize                   (validation loss, per-class IoU, mIoU: one fused pass per batch)
+    class_weights                         (nn.CrossEntropyLoss(weight=...) from pixel counts or a confusion matrix)
     Adam                                  (main.py:100's optimizer, one-launch HIP step)
     traceable                             (pure-torch CPU twin for convert.py's ONNX export)
     Predictor, preprocess_image           (inference.py's per-frame path)
@@ -16,7 +17,7 @@ All compute runs in libsegamd.so (HIP, gfx950); see include/segamd.h.
 """
 from .unet import MobileNetV2UNet, UNet, LightUNet, double_conv, inconv, down, up, outconv  # noqa: F401
 from .train import train_model, train_one_epoch, validate  # noqa: F401
-from .metrics import summarize  # noqa: F401
+from .metrics import class_weights, summarize  # noqa: F401
 from .detinit import deterministic_init, synthetic_batch  # noqa: F401
 from .data import CombinedLaneDataset, DistributedWeightedSampler, reference_sample_weights  # noqa: F401
 from .infer import Predictor, preprocess_image  # noqa: F401
@@ -25,7 +26,8 @@ from .optim import Adam  # noqa: F401
 from .export import traceable  # noqa: F401
 
 __all__ = ["MobileNetV2UNet", "UNet", "LightUNet", "double_conv", "inconv", "down", "up", "outconv",
-           "train_model", "train_one_epoch", "validate", "summarize", "deterministic_init", "synthetic_batch",
+           "train_model", "train_one_epoch", "validate", "summarize", "class_weights", "deterministic_init",
+           "synthetic_batch",
            "CombinedLaneDataset", "DistributedWeightedSampler", "reference_sample_weights",
            "Predictor", "preprocess_image", "Overlay", "overlay_predictions", "COLOR_MAP",
            "Adam", "traceable"]

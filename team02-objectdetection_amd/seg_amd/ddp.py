@@ -321,14 +321,21 @@ class DataParallel(nn.Module):
         self._pre(x)
         return self.module(x)
 
-    def forward_loss(self, x, target, ignore_index: int = -100):
+    def forward_loss(self, x, target, ignore_index: int = -100, weight=None, label_smoothing: float = 0.0,
+                     reduction: str = "mean"):
+        """The module's forward_loss on this rank's shard.  With class weights and reduction "mean"
+        each rank normalises by its OWN shard's D = sum of w[label] over its valid pixels, and the
+        gradients are then averaged over the ranks -- what torch's DistributedDataParallel does with
+        a weighted criterion; it is not the weighted mean over the global batch unless the shards'
+        D agree."""
         self._pre(x)
-        return self.module.forward_loss(x, target, ignore_index)
+        return self.module.forward_loss(x, target, ignore_index, weight, label_smoothing, reduction)
 
-    def forward_metrics(self, x, target, confusion, ignore_index: int = -100):
+    def forward_metrics(self, x, target, confusion, ignore_index: int = -100, weight=None,
+                        label_smoothing: float = 0.0, reduction: str = "mean"):
         """Validation step of this rank's shard: no gradients, so no bucket is armed and nothing is
         broadcast; seg_amd.validate sums the ranks' matrices and losses with its own all-reduces."""
-        return self.module.forward_metrics(x, target, confusion, ignore_index)
+        return self.module.forward_metrics(x, target, confusion, ignore_index, weight, label_smoothing, reduction)
 
     def state_dict(self, *args, **kwargs):
         return self.module.state_dict(*args, **kwargs)

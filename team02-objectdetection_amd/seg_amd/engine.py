@@ -1576,13 +1576,53 @@ def _check_input(x: torch.Tensor):
         raise NotImplementedError("gradient w.r.t. the input image is not supported")
 
 
-def _loss_forward(run, t, ignore_index, confusion=None):
+REDUCTIONS = {"mean": 0, "sum": 1}  # the C ABI's `reduction` (include/segamd.h: seg_cew_*)
+
+
+def loss_options(weight, label_smoothing, reduction, C, device):
+    """The checked (weight, label_smoothing, reduction) of a fused loss over C classes on `device`; ValueError for
+    what the kernels do not take.  nn.CrossEntropyLoss's options for class-index targets, reduction "none" apart."""
+    if reduction not in REDUCTIONS:
+        raise ValueError(f"reduction must be 'mean' or 'sum' for the fused loss, got {reduction!r}")
+    eps = float(label_smoothing)
+    if not 0.0 <= eps <= 1.0:
+        raise ValueError(f"label_smoothing must be in [0, 1], got {label_smoothing!r}")
+    if weight is not None:
+        if not isinstance(weight, torch.Tensor) or weight.dtype != torch.float32 or tuple(weight.shape) != (C,) \
+                or weight.device != device or not weight.is_contiguous():
+            what = (f"{tuple(weight.shape)} {weight.dtype} on {weight.device}" if isinstance(weight, torch.Tensor)
+                    else type(weight).__name__)
+            raise ValueError(f"weight must be a contiguous float32 [{C}] tensor on {device}, got {what}")
+        weight = weight.detach()
+    return weight, eps, reduction
+
+
+def _plain_loss(weight, label_smoothing, reduction):
+    return weight is None and label_smoothing == 0.0 and reduction == "mean"
+
+
+def _loss_forward(run, t, ignore_index, confusion=None, weight=None, label_smoothing=0.0, reduction="mean"):
     """Fused final upsample + CrossEntropy over the run's low-res logits: stats = [loss, count, #bad labels].
     confusion (int64 [C, C], "metrics" mode): the same pass also adds every valid pixel to
-    confusion[label, argmax] (seg_ce_upsample_eval)."""
+    confusion[label, argmax] (seg_ce_upsample_eval).  With class weights, label smoothing or reduction "sum"
+    (loss_options) the seg_cew_* kernels run instead: stats = [loss, D, #bad labels, #valid], same first three slots."""
     prog, lo, s = run.prog, run.prog.logits, run.stream
     N = prog.N
     Ho, Wo = prog.out_hw
+    run.target, run.weight, run.label_smoothing = t, weight, label_smoothing
+    run.plain_loss = _plain_loss(weight, label_smoothing, reduction)
+    if not run.plain_loss:
+        stats = run.tmp(4)  # loss, D, #out-of-range labels, #valid
+        work = run.tmp(query("seg_cew_workspace_floats", N * Ho * Wo))
+        args = (run.ptr(lo), lo.ld, N, lo.H, lo.W, lo.C, t.data_ptr(), Ho, Wo, ignore_index,
+                weight.data_ptr() if weight is not None else 0, label_smoothing, REDUCTIONS[reduction],
+                work.data_ptr(), stats.data_ptr())
+        if confusion is None:
+            run.call(run.k("seg_cew_upsample_loss"), *args, s)
+        else:
+            run.call(run.k("seg_cew_upsample_eval"), *args, confusion.data_ptr(), s)
+        run.stats = stats
+        return stats
     stats = run.tmp(3)  # loss, #valid, #out-of-range labels
     work = run.tmp(query("seg_ce_workspace_floats", N * Ho * Wo))
     if confusion is None:
@@ -1602,8 +1642,14 @@ def _loss_backward(run, g, ignore_index):
     Ho, Wo = prog.out_hw
     dhigh = torch.empty(max(N * Ho * Wo * lo.ld, 1), device=run.device, dtype=run.store)
     run.keep.append(dhigh)
-    run.call(run.k("seg_ce_upsample_grad"), run.ptr(lo), lo.ld, N, lo.H, lo.W, lo.C, run.target.data_ptr(), Ho, Wo,
-             ignore_index, g.data_ptr(), run.stats.data_ptr(), dhigh.data_ptr(), lo.ld, s)
+    if run.plain_loss:
+        run.call(run.k("seg_ce_upsample_grad"), run.ptr(lo), lo.ld, N, lo.H, lo.W, lo.C, run.target.data_ptr(), Ho,
+                 Wo, ignore_index, g.data_ptr(), run.stats.data_ptr(), dhigh.data_ptr(), lo.ld, s)
+    else:  # the forward's options (_loss_forward)
+        w = run.weight
+        run.call(run.k("seg_cew_upsample_grad"), run.ptr(lo), lo.ld, N, lo.H, lo.W, lo.C, run.target.data_ptr(), Ho,
+                 Wo, ignore_index, w.data_ptr() if w is not None else 0, run.label_smoothing, g.data_ptr(),
+                 run.stats.data_ptr(), dhigh.data_ptr(), lo.ld, s)
     run.call(run.k("seg_upsample_bwd"), dhigh.data_ptr(), lo.ld, 0, N, Ho, Wo, lo.C, run.gptr(lo), lo.ld, lo.H, lo.W,
              1, 0, s)
     run.mark_written(lo)
@@ -1618,19 +1664,23 @@ class Plan:
     the side stream, DataParallel bucket all-reduces at host-callback stops).  Recorded
     by the first step -- a normal program walk with every launch captured instead of
     issued -- and replayed by the following ones with the caller's input / target /
-    output / upstream-gradient pointers patched in.  Buffers, workspaces, saved BN
+    class-weight / output / upstream-gradient pointers patched in (label smoothing and the
+    reduction are part of the plan's key; the weight VALUES are read by the kernels each step).  Buffers, workspaces, saved BN
     statistics and the flat parameter-gradient buffer are persistent (allocated while
     recording, ~13 GB at bs=32 256x512 fp32 -- nothing is recomputed).
 
     The replay issues the same launches on the same two streams as an eager walk, so
     results are bitwise those of the eager engine (tests/test_gpu_tape.py)."""
 
-    def __init__(self, prog, training, mode, ignore_index, sync, needs_grad, device):
+    def __init__(self, prog, training, mode, ignore_index, sync, needs_grad, device, label_smoothing=0.0,
+                 reduction="mean"):
         self.prog, self.training, self.mode, self.ignore_index = prog, training, mode, ignore_index
+        self.label_smoothing, self.reduction = label_smoothing, reduction
         self.sync, self.needs_grad, self.device = sync, needs_grad, device
         self.side = _side_stream(device) if (OVERLAP and needs_grad) else None
         self.run = self.fwd = self.bwd = None
         self.t = None            # the last forward's labels (loss mode)
+        self.w = None            # the last forward's class weights (None: unweighted)
         self.busy = False        # a forward whose backward has not run yet
         self.timer = None        # the KernelTimer the tapes' timing is armed for
         self.fp = None           # _fingerprint(prog) the tapes were recorded against
@@ -1651,7 +1701,7 @@ class Plan:
             tape.time(TIMER.kinds, TIMER.max_replays)
             TIMER.tapes.append(tape)
 
-    def forward(self, x, t, confusion=None):
+    def forward(self, x, t, confusion=None, weight=None):
         from .tape import Recorder
         main, side = self._streams()
         N, _, H, W = x.shape
@@ -1668,6 +1718,8 @@ class Plan:
                 rec.external("out", out.data_ptr())
             if confusion is not None:
                 rec.external("confusion", confusion.data_ptr())
+            if weight is not None:
+                rec.external("w", weight.data_ptr())
             run = Run(self.prog, x, self.training, rec=rec, side=self.side)
             run.sync = self.sync
             if self.needs_grad:
@@ -1683,14 +1735,15 @@ class Plan:
                 run.call(run.k("seg_upsample_to_nchw"), run.ptr(lo), lo.ld, N, lo.H, lo.W, lo.C, out.data_ptr(), Ho,
                          Wo, 1, run.stream)
             else:
-                _loss_forward(run, t, self.ignore_index, confusion)
+                _loss_forward(run, t, self.ignore_index, confusion, weight, self.label_smoothing, self.reduction)
             run.rec = None
             self.run, self.fwd = run, rec.build()
         self._arm_timer(self.fwd)
-        self.t = t  # the backward tape reads the labels: keep them alive until then
+        self.t, self.w = t, weight  # the backward tape reads the labels and the weights: keep them alive until then
         self.fwd.bind(x=x.data_ptr(), t=t.data_ptr() if t is not None else 0,
                       out=out.data_ptr() if out is not None else 0,
-                      confusion=confusion.data_ptr() if confusion is not None else 0)
+                      confusion=confusion.data_ptr() if confusion is not None else 0,
+                      w=weight.data_ptr() if weight is not None else 0)
         self.fwd.run(main, side)
         if DEBUG_KEEP_RUN:
             global LAST_RUN
@@ -1712,6 +1765,10 @@ class Plan:
             rec.external("gout", g.data_ptr())
             if self.t is not None:
                 rec.external("t", self.t.data_ptr())
+                run.target = self.t
+            if self.w is not None:
+                rec.external("w", self.w.data_ptr())
+                run.weight = self.w
             run.rec = rec
             if self.mode == "logits":
                 prog, lo = self.prog, self.prog.logits
@@ -1725,7 +1782,8 @@ class Plan:
             run.rec = None
             self.bwd = rec.build()
         self._arm_timer(self.bwd)
-        self.bwd.bind(gout=g.data_ptr(), t=self.t.data_ptr() if self.t is not None else 0)
+        self.bwd.bind(gout=g.data_ptr(), t=self.t.data_ptr() if self.t is not None else 0,
+                      w=self.w.data_ptr() if self.w is not None else 0)
         self.bwd.run(main, side)
         if DEBUG_KEEP_RUN:
             global LAST_RUN
@@ -1761,15 +1819,19 @@ def release_plans(model):
     model.__dict__.pop("_segamd_plans", None)
 
 
-def _plan(model, prog, mode, ignore_index, sync, needs_grad, device):
+def _plan(model, prog, mode, ignore_index, sync, needs_grad, device, opts=(None, 0.0, "mean")):
+    """opts: loss_options().  The weight tensor itself is no part of the key (only whether there is one): its
+    pointer is patched into the tapes per replay, so new weight values or a new weight tensor need no new plan."""
     cache = model.__dict__.setdefault("_segamd_plans", {})
-    key = (id(prog), mode, model.training, ignore_index, id(sync) if sync is not None else None, needs_grad, OVERLAP)
+    weight, eps, reduction = opts
+    key = (id(prog), mode, model.training, ignore_index, id(sync) if sync is not None else None, needs_grad, OVERLAP,
+           (eps, reduction, weight is None))
     fp = _fingerprint(prog)
     plan = cache.pop(key, None)  # re-inserted below: dict order = least recently used first
     if plan is None or plan.sync is not sync or plan.fp != fp:
         if plan is not None and plan.busy:
             raise RuntimeError("segamd: parameters or buffers were rebound between a forward and its backward")
-        plan = Plan(prog, model.training, mode, ignore_index, sync, needs_grad, device)
+        plan = Plan(prog, model.training, mode, ignore_index, sync, needs_grad, device, eps, reduction)
         plan.fp = fp
     cache[key] = plan
     while len(cache) > max(MAX_PLANS, 1):
@@ -1780,7 +1842,7 @@ def _plan(model, prog, mode, ignore_index, sync, needs_grad, device):
     if plan.busy:
         # a second forward before this plan's backward ran: a one-off plan keeps the first
         # forward's activations intact (recorded and run once, then dropped)
-        plan = Plan(prog, model.training, mode, ignore_index, sync, needs_grad, device)
+        plan = Plan(prog, model.training, mode, ignore_index, sync, needs_grad, device, eps, reduction)
         plan.fp = fp
     return plan
 
@@ -1808,7 +1870,7 @@ class _SegFunction(torch.autograd.Function):
     """Whole-network forward/backward as one autograd node (replaying the plan's tapes)."""
 
     @staticmethod
-    def forward(ctx, model, mode, x, target, ignore_index, sync, *params):
+    def forward(ctx, model, mode, x, target, ignore_index, sync, opts, *params):
         x = x.contiguous()
         N, _, H, W = x.shape
         prog = get_program(model, N, H, W)
@@ -1818,9 +1880,11 @@ class _SegFunction(torch.autograd.Function):
             t = target.contiguous()
             if t.dtype != torch.int64 or tuple(t.shape) != (N, Ho, Wo):
                 raise ValueError(f"target must be int64 [{N},{Ho},{Wo}], got {tuple(t.shape)} {t.dtype}")
-        needs_grad = any(ctx.needs_input_grad[6:])
-        plan = _plan(model, prog, mode, ignore_index, sync, needs_grad, x.device)
-        out = plan.forward(x, t)
+        needs_grad = any(ctx.needs_input_grad[7:])
+        if mode == "loss":
+            opts = loss_options(*opts, prog.logits.C, x.device)
+        plan = _plan(model, prog, mode, ignore_index, sync, needs_grad, x.device, opts)
+        out = plan.forward(x, t, weight=opts[0])
         if mode == "loss":
             out = _publish_stats(model, plan.run.stats)
         else:  # an unfused criterion checks its own labels: no stale flag from an earlier fused loss
@@ -1853,9 +1917,9 @@ class _SegFunction(torch.autograd.Function):
             for p in ctx.params:
                 slot = run.flat_slots.get(id(p)) if id(p) in run.grads else None
                 grads.append(flat[slot[0]:slot[0] + slot[1]].view_as(p) if slot else None)
-        grads = [g if ctx.needs_input_grad[6 + k] else None for k, g in enumerate(grads)]
+        grads = [g if ctx.needs_input_grad[7 + k] else None for k, g in enumerate(grads)]
         ctx.plan = ctx.params = None
-        return (None, None, None, None, None, None, *grads)
+        return (None, None, None, None, None, None, None, *grads)
 
 
 def bad_label_count(model):
@@ -1913,21 +1977,28 @@ def _params_for(model, x):
 def run_logits(model, x: torch.Tensor) -> torch.Tensor:
     _check_input(x)
     sync = model.__dict__.get("_segamd_sync")
-    return _SegFunction.apply(model, "logits", x, None, IGNORE_INDEX, sync, *_params_for(model, x))
+    return _SegFunction.apply(model, "logits", x, None, IGNORE_INDEX, sync, (None, 0.0, "mean"),
+                              *_params_for(model, x))
 
 
-def run_loss(model, x: torch.Tensor, target: torch.Tensor, ignore_index: int = IGNORE_INDEX) -> torch.Tensor:
+def run_loss(model, x: torch.Tensor, target: torch.Tensor, ignore_index: int = IGNORE_INDEX, weight=None,
+             label_smoothing: float = 0.0, reduction: str = "mean") -> torch.Tensor:
+    """nn.CrossEntropyLoss(weight, ignore_index=..., reduction=..., label_smoothing=...)(model(x), target) with the
+    loss fused into the final upsample (csrc/loss.hip); the options are checked by loss_options (ValueError)."""
     _check_input(x)
     sync = model.__dict__.get("_segamd_sync")
-    return _SegFunction.apply(model, "loss", x, target, ignore_index, sync, *_params_for(model, x))
+    return _SegFunction.apply(model, "loss", x, target, ignore_index, sync, (weight, label_smoothing, reduction),
+                              *_params_for(model, x))
 
 
 @torch.no_grad()
 def run_metrics(model, x: torch.Tensor, target: torch.Tensor, confusion: torch.Tensor,
-                ignore_index: int = IGNORE_INDEX) -> torch.Tensor:
+                ignore_index: int = IGNORE_INDEX, weight=None, label_smoothing: float = 0.0,
+                reduction: str = "mean") -> torch.Tensor:
     """Validation forward: the fused loss of run_loss, and in the same kernel
     confusion[label, argmax of the full-resolution logits] += 1 for every valid pixel
-    (csrc/loss.hip: seg_ce_upsample_eval).  A forward tape only: no gradient is ever built, so
+    (csrc/loss.hip: seg_ce_upsample_eval, or seg_cew_upsample_eval with loss options -- they change
+    the returned loss only, never the matrix).  A forward tape only: no gradient is ever built, so
     DataParallel's buckets are not involved (sync is None).  Plans are keyed by model.training
     like the others: eval() uses the running statistics, train() the batch's."""
     _check_input(x)
@@ -1944,6 +2015,7 @@ def run_metrics(model, x: torch.Tensor, target: torch.Tensor, confusion: torch.T
             or not confusion.is_contiguous()):
         raise ValueError(f"confusion must be a contiguous int64 [{C},{C}] tensor on {x.device}, got "
                          f"{tuple(confusion.shape)} {confusion.dtype} on {confusion.device}")
-    plan = _plan(model, prog, "metrics", ignore_index, None, False, x.device)
-    plan.forward(x, t, confusion)
+    opts = loss_options(weight, label_smoothing, reduction, C, x.device)
+    plan = _plan(model, prog, "metrics", ignore_index, None, False, x.device, opts)
+    plan.forward(x, t, confusion, opts[0])
     return _publish_stats(model, plan.run.stats)

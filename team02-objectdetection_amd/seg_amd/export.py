@@ -91,24 +91,30 @@ class TorchMobileNetV2UNet(MobileNetV2UNet):
     def forward(self, x):
         return torch_forward(self, x)
 
-    def forward_loss(self, x, target, ignore_index: int = -100):
-        return nn.functional.cross_entropy(self(x), target, ignore_index=ignore_index)
+    def forward_loss(self, x, target, ignore_index: int = -100, weight=None, label_smoothing: float = 0.0,
+                     reduction: str = "mean"):
+        return nn.functional.cross_entropy(self(x), target, weight, ignore_index=ignore_index, reduction=reduction,
+                                           label_smoothing=label_smoothing)
 
-    def forward_metrics(self, x, target, confusion, ignore_index: int = -100):
+    def forward_metrics(self, x, target, confusion, ignore_index: int = -100, weight=None,
+                        label_smoothing: float = 0.0, reduction: str = "mean"):
         from .unet import _torch_metrics
-        return _torch_metrics(self, x, target, confusion, ignore_index)
+        return _torch_metrics(self, x, target, confusion, ignore_index, weight, label_smoothing, reduction)
 
 
 class _TorchUNetMixin:
     def forward(self, x):
         return torch_forward(self, x)
 
-    def forward_loss(self, x, target, ignore_index: int = -100):
-        return nn.functional.cross_entropy(self(x), target, ignore_index=ignore_index)
+    def forward_loss(self, x, target, ignore_index: int = -100, weight=None, label_smoothing: float = 0.0,
+                     reduction: str = "mean"):
+        return nn.functional.cross_entropy(self(x), target, weight, ignore_index=ignore_index, reduction=reduction,
+                                           label_smoothing=label_smoothing)
 
-    def forward_metrics(self, x, target, confusion, ignore_index: int = -100):
+    def forward_metrics(self, x, target, confusion, ignore_index: int = -100, weight=None,
+                        label_smoothing: float = 0.0, reduction: str = "mean"):
         from .unet import _torch_metrics
-        return _torch_metrics(self, x, target, confusion, ignore_index)
+        return _torch_metrics(self, x, target, confusion, ignore_index, weight, label_smoothing, reduction)
 
 
 class TorchUNet(_TorchUNetMixin, UNet):

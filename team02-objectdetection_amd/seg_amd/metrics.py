@@ -40,3 +40,33 @@ def summarize(confusion: torch.Tensor) -> dict:
             "pixel_acc": float(tp.sum() / total) if total > 0 else float("nan"),
             "iou": iou,
             "miou": float(iou[valid].mean()) if valid.any() else float("nan")}
+
+
+def class_weights(counts, scheme: str = "median_frequency", clip: float | None = None) -> torch.Tensor:
+    """Class weights for nn.CrossEntropyLoss(weight=...) from pixel counts: a float32 CPU [C] tensor.
+
+    counts: a length-C vector of label pixel counts, or a [C, C] confusion matrix (row = label), whose
+    row sums are those counts -- validate()["confusion"] as it stands.
+    scheme: "median_frequency": w_c = median(n) / n_c, the median taken over the classes that occur
+    (the lower one of an even number, so the class at the median gets exactly 1.0);
+    "inverse": w_c = sum(n) / (#classes that occur * n_c), which averages to 1 over the pixels.
+    A class that never occurs gets weight 0.  clip: an upper bound applied last."""
+    n = torch.as_tensor(counts).detach().to("cpu", torch.float64)
+    if n.dim() == 2 and n.shape[0] == n.shape[1]:
+        n = n.sum(1)
+    if n.dim() != 1 or n.numel() == 0 or bool((n < 0).any()):
+        raise ValueError("counts must be a non-negative length-C vector or a [C, C] confusion matrix")
+    present = n > 0
+    w = torch.zeros_like(n)
+    if present.any():
+        if scheme == "median_frequency":
+            w[present] = n[present].median() / n[present]
+        elif scheme == "inverse":
+            w[present] = n.sum() / (int(present.sum()) * n[present])
+        else:
+            raise ValueError(f"scheme must be 'median_frequency' or 'inverse', got {scheme!r}")
+    elif scheme not in ("median_frequency", "inverse"):
+        raise ValueError(f"scheme must be 'median_frequency' or 'inverse', got {scheme!r}")
+    if clip is not None:
+        w = w.clamp(max=float(clip))
+    return w.to(torch.float32)

@@ -6,10 +6,11 @@ running loss, a per-epoch "Training Loss" line and a state_dict checkpoint
 `Models/obj/obj_MOB_1_epoch_{epoch}.pth` (src/train.py:77).
 
 MI355X differences (results are the same):
-  * when `criterion` is a plain `nn.CrossEntropyLoss()` (main.py:99) and the
-    model is a seg_amd model, the loss is computed by the fused
-    upsample+cross-entropy kernels (`model.forward_loss`), so the 168 MB of
-    full-resolution logits per bs=32 batch are never written;
+  * when `criterion` is an `nn.CrossEntropyLoss` (main.py:99; class weights,
+    label smoothing and reduction "mean" / "sum" included) and the model is a
+    seg_amd model, the loss is computed by the fused upsample+cross-entropy
+    kernels (`model.forward_loss`), so the 168 MB of full-resolution logits
+    per bs=32 batch are never written;
   * under torch.distributed the gradients are averaged across ranks by
     seg_amd.ddp (RCCL all-reduce overlapped with the backward) and only
     rank 0 prints and writes checkpoints.
@@ -28,9 +29,17 @@ except ImportError:  # pragma: no cover
     tqdm = None
 
 
-def _fusable_ce(criterion) -> bool:
-    return (isinstance(criterion, nn.CrossEntropyLoss) and criterion.weight is None
-            and criterion.reduction == "mean" and criterion.label_smoothing == 0.0)
+def fused_loss_options(criterion):
+    """The keyword arguments of model.forward_loss / forward_metrics that reproduce `criterion`, or
+    None when it has to run on the full-resolution logits: anything but an nn.CrossEntropyLoss
+    (a subclass with a forward of its own included), and reduction="none", whose result is a
+    full-resolution tensor."""
+    if not isinstance(criterion, nn.CrossEntropyLoss) or type(criterion).forward is not nn.CrossEntropyLoss.forward:
+        return None
+    if criterion.reduction not in ("mean", "sum"):
+        return None
+    return {"ignore_index": criterion.ignore_index, "weight": criterion.weight,
+            "label_smoothing": float(criterion.label_smoothing), "reduction": criterion.reduction}
 
 
 def _is_rank0() -> bool:
@@ -100,8 +109,9 @@ def _step_and_loss(model, inputs, optimizer, loss):
 def compute_loss(model, criterion, inputs, targets):
     """criterion(model(inputs), targets), fused when the pair allows it."""
     core = getattr(model, "module", model)
-    if hasattr(core, "forward_loss") and _fusable_ce(criterion):
-        return model.forward_loss(inputs, targets, criterion.ignore_index)
+    opts = fused_loss_options(criterion) if hasattr(core, "forward_loss") else None
+    if opts is not None:
+        return model.forward_loss(inputs, targets, **opts)
     return criterion(model(inputs), targets)
 
 
@@ -159,9 +169,10 @@ def validate(model, val_loader, criterion, device, progress: bool = True, epoch:
     Returns {"loss": mean of the batch means (val_loss += loss.item(); / len(val_loader)),
     "confusion", "pixel_acc", "iou", "miou"}.  The previous train/eval mode is restored.
 
-    When `criterion` is a plain nn.CrossEntropyLoss() and the model has `forward_metrics`, each
-    batch is one fused forward (loss + argmax + confusion matrix from the low-resolution
-    logits); any other pair runs criterion(model(x), t) with argmax and bincount on the
+    When `criterion` is an nn.CrossEntropyLoss (fused_loss_options: class weights, label smoothing
+    and reduction "mean" / "sum" included -- they change "loss" only, never the matrix) and the
+    model has `forward_metrics`, each batch is one fused forward (loss + argmax + confusion matrix
+    from the low-resolution logits); any other pair runs criterion(model(x), t) with argmax and bincount on the
     device.  Either way the batch losses and the matrix stay on the device and the host waits
     once, at the end of the pass -- so the bar shows no per-batch loss.  An out-of-range label
     raises IndexError there.  Under torch.distributed every rank evaluates its own shard; the
@@ -170,7 +181,8 @@ def validate(model, val_loader, criterion, device, progress: bool = True, epoch:
     from .metrics import add_confusion, summarize
     core = getattr(model, "module", model)
     ignore_index = getattr(criterion, "ignore_index", -100)
-    fused = hasattr(core, "forward_metrics") and _fusable_ce(criterion)
+    opts = fused_loss_options(criterion) if hasattr(core, "forward_metrics") else None
+    fused = opts is not None
     it = val_loader
     if progress and tqdm is not None and _is_rank0():
         it = tqdm(val_loader, desc=f"Epoch {epoch + 1}/{epochs} [Valid]", leave=True, position=0,
@@ -189,7 +201,7 @@ def validate(model, val_loader, criterion, device, progress: bool = True, epoch:
                     if confusion is None:
                         C = _num_classes(core)
                         confusion = torch.zeros((C, C), dtype=torch.int64, device=inputs.device)
-                    loss = model.forward_metrics(inputs, targets, confusion, ignore_index)
+                    loss = model.forward_metrics(inputs, targets, confusion, **opts)
                     if inputs.is_cuda:  # the CPU composition's F.cross_entropy raises by itself
                         from .engine import bad_label_count
                         acc[2] += bad_label_count(model)[0]

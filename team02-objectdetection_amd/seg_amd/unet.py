@@ -80,32 +80,42 @@ class _SegModel(nn.Module):
         from .engine import run_logits
         return run_logits(self, x)
 
-    def forward_loss(self, x: torch.Tensor, target: torch.Tensor, ignore_index: int = -100) -> torch.Tensor:
+    def forward_loss(self, x: torch.Tensor, target: torch.Tensor, ignore_index: int = -100, weight=None,
+                     label_smoothing: float = 0.0, reduction: str = "mean") -> torch.Tensor:
         """nn.CrossEntropyLoss()(self(x), target) (main.py:99, src/train.py:37) fused
-        with the final upsample: the full-resolution logits are never stored."""
+        with the final upsample: the full-resolution logits are never stored.
+
+        weight (float32 [C] on x's device), label_smoothing (in [0, 1]) and reduction ("mean" |
+        "sum") are nn.CrossEntropyLoss's for class-index targets and stay fused; anything else
+        (reduction="none" included) is a ValueError.  The weight tensor is read when the kernels
+        run: editing it in place or passing another one needs no new launch plan."""
         if x.device.type == "cpu":
-            return nn.functional.cross_entropy(self(x), target, ignore_index=ignore_index)
+            return nn.functional.cross_entropy(self(x), target, weight, ignore_index=ignore_index,
+                                               reduction=reduction, label_smoothing=label_smoothing)
         from .engine import run_loss
-        return run_loss(self, x, target, ignore_index)
+        return run_loss(self, x, target, ignore_index, weight, label_smoothing, reduction)
 
     def forward_metrics(self, x: torch.Tensor, target: torch.Tensor, confusion: torch.Tensor,
-                        ignore_index: int = -100) -> torch.Tensor:
+                        ignore_index: int = -100, weight=None, label_smoothing: float = 0.0,
+                        reduction: str = "mean") -> torch.Tensor:
         """Validation step: returns nn.CrossEntropyLoss()(self(x), target) and adds every
         non-ignored pixel to `confusion[label, argmax(self(x))]` (int64 [C, C] on x's device, in
         place), without gradients.  On the MI355X one kernel does both from the low-resolution
-        logits: the full-resolution logits are never stored."""
+        logits: the full-resolution logits are never stored.  weight, label_smoothing and
+        reduction (as in forward_loss) change the returned loss only, never the matrix."""
         if x.device.type == "cpu":
-            return _torch_metrics(self, x, target, confusion, ignore_index)
+            return _torch_metrics(self, x, target, confusion, ignore_index, weight, label_smoothing, reduction)
         from .engine import run_metrics
-        return run_metrics(self, x, target, confusion, ignore_index)
+        return run_metrics(self, x, target, confusion, ignore_index, weight, label_smoothing, reduction)
 
 
 @torch.no_grad()
-def _torch_metrics(model, x, target, confusion, ignore_index):
+def _torch_metrics(model, x, target, confusion, ignore_index, weight=None, label_smoothing=0.0, reduction="mean"):
     """forward_metrics in torch ops (CPU tensors): F.cross_entropy raises on an out-of-range label by itself."""
     from .metrics import add_confusion
     logits = model(x)
-    loss = nn.functional.cross_entropy(logits, target, ignore_index=ignore_index)
+    loss = nn.functional.cross_entropy(logits, target, weight, ignore_index=ignore_index, reduction=reduction,
+                                       label_smoothing=label_smoothing)
     add_confusion(confusion, logits.argmax(1), target, ignore_index)
     return loss
 
