@@ -339,6 +339,15 @@ int seg_bn_bwd_apply(const float* da, long ldda, const float* y, long ldy, long 
 int seg_bn_eval_backward(const float* da, long ldda, const float* y, long ldy, long M, int C,
                          const float* scale, const float* shift, int act, float* dy, long lddy,
                          hipStream_t stream);
+/* Backward through a BatchNorm on frozen (running) statistics, scale / shift from seg_bn_eval_coef, in one pass
+ * over da and y: dy = scale * dz, dbeta = sum(dz), dgamma = sum(dz * (y - running_mean)) / sqrt(running_var + eps),
+ * dz = da * act'(y*scale + shift).  dgamma == dbeta == NULL: no reduction, the elementwise pass alone
+ * (seg_bn_eval_backward's dy); dy == NULL: the affine gradients alone.  work >= seg_chan_workspace_floats(M, C)
+ * floats (unused without an affine gradient).  Fixed-order sums: bitwise reproducible, fp32 and bf16io alike. */
+int seg_bn_frozen_backward(const float* da, long ldda, const float* y, long ldy, long M, int C,
+                           const float* scale, const float* shift, const float* running_mean,
+                           const float* running_var, float eps, int act, float* dgamma, float* dbeta,
+                           float* work, float* dy, long lddy, hipStream_t stream);
 /* conv bias gradient: out[c] (+)= sum_r y[r][c]; work >= seg_chan_workspace_floats(M, round_up(C, 4)) */
 int seg_colsum(const float* y, long ldy, long M, int C, float* work, float* out, int accumulate,
                hipStream_t stream);
@@ -484,6 +493,9 @@ int seg_bn_apply_bf16io(const seg_bf16* y, long ldy, long M, int C, const float*
 int seg_bn_backward_bf16io(const seg_bf16* da, long ldda, const seg_bf16* y, long ldy, long M, int C, const float*
     gamma, const float* mean, const float* invstd, const float* scale, const float* shift, int act, float* dgamma,
     float* dbeta, float* work, seg_bf16* dy, long lddy, hipStream_t stream);
+int seg_bn_frozen_backward_bf16io(const seg_bf16* da, long ldda, const seg_bf16* y, long ldy, long M, int C,
+    const float* scale, const float* shift, const float* running_mean, const float* running_var, float eps, int act,
+    float* dgamma, float* dbeta, float* work, seg_bf16* dy, long lddy, hipStream_t stream);
 int seg_colsum_bf16io(const seg_bf16* y, long ldy, long M, int C, float* work, float* out, int accumulate, hipStream_t
     stream);
 int seg_dw_fwd_bf16io(const seg_bf16* in, long ldin, int N, int H, int W, int C, const float* in_scale, const float*

@@ -180,6 +180,116 @@ void launch_chan_partial(const T* y, long ldy, const T* da, long ldda, long M, i
                        0, stream, y, ldy, da, ldda, (int)M, C, scale, shift, mean, act, part, rpb);
 }
 
+template <int VW, typename T>
+__device__ __forceinline__ void stw(T* p, const f32x4 (&o)[VW / 4]) {
+  if constexpr (VW == 8 && sizeof(T) == 2) {
+    const bf16x4 lo = __builtin_convertvector(o[0], bf16x4), hi = __builtin_convertvector(o[1], bf16x4);
+    *reinterpret_cast<bf16x8*>(p) = seg_cat8(lo, hi);
+  } else {
+#pragma unroll
+    for (int j = 0; j < VW / 4; ++j) st4(p + 4 * j, o[j]);
+  }
+}
+
+// Backward through a BatchNorm on frozen (running) statistics, one pass: the normalisation is a fixed affine map,
+// so dY = scale * dz (dz = dA * act'(y*scale+shift)) needs no reduction and is stored from the pass that sums
+// kind 1's partials (sum(dz), sum(dz*(y - running_mean))) -- dA and y are read once (3 |Y| against the train-mode
+// backward's 5 |Y|).  The block / lane / row partition, the row order and the row-group tree are
+// chan_partial_kernel's, so the partials follow the family's reduction order (fp32 and bf16io alike).  RED = false:
+// no affine gradient wanted, the elementwise pass alone (no LDS); dy == nullptr: nothing upstream wants dY, the
+// partials alone.
+template <typename T, int VW, bool RED>
+__global__ __launch_bounds__(kRedThreads) void bn_frozen_bwd_kernel(
+    const T* __restrict__ y, long ldy, const T* __restrict__ da, long ldda, int M, int C,
+    const float* __restrict__ scale, const float* __restrict__ shift, const float* __restrict__ mean, int act,
+    float* __restrict__ part, T* dy, long lddy, int rows_per_block) {
+  constexpr int NV = VW / 4;
+  __shared__ f32x4 red0[RED ? kRedThreads * NV : 1], red1[RED ? kRedThreads * NV : 1];
+  const int CG = C / VW;
+  const int cg0 = blockIdx.y * kRedSlice;
+  const int TC = min(CG - cg0, kRedSlice);
+  const int RG = kRedThreads / TC;
+  const int t = threadIdx.x;
+  const int rg = t / TC, tc = t - rg * TC;
+  const bool active = rg < RG;
+  const int r0 = blockIdx.x * rows_per_block;
+  const int r1 = min(M, r0 + rows_per_block);
+  const int c = (cg0 + tc) * VW;
+  f32x4 s0[NV], s1[NV], k[NV], sc[NV], sh[NV];
+#pragma unroll
+  for (int j = 0; j < NV; ++j) s0[j] = s1[j] = k[j] = sc[j] = sh[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  if (active) {
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+      if (RED) k[j] = ld4(mean + c + 4 * j);
+      sc[j] = ld4(scale + c + 4 * j);
+      sh[j] = ld4(shift + c + 4 * j);
+    }
+    auto step = [&](int r, const f32x4 (&v)[NV], const f32x4 (&g)[NV]) {
+      f32x4 o[NV];
+#pragma unroll
+      for (int j = 0; j < NV; ++j) {
+        f32x4 dz;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) dz[e] = g[j][e] * seg_act_mask(v[j][e] * sc[j][e] + sh[j][e], act);
+        if (RED) {
+          s0[j] += dz;
+          s1[j] += dz * (v[j] - k[j]);
+        }
+        o[j] = dz * sc[j];
+      }
+      if (dy) stw<VW>(dy + (long)r * lddy + c, o);
+    };
+    // one row's loads per trip on 8-lane fp32 (chan_partial_kernel's register budget), four otherwise
+    constexpr int RQ = (sizeof(T) == 4 && VW == 8) ? SEG_RQ : 4;
+    int r = r0 + rg;
+    for (; r + (RQ - 1) * RG < r1; r += RQ * RG) {
+      f32x4 v[RQ][NV], g[RQ][NV];
+#pragma unroll
+      for (int q = 0; q < RQ; ++q) {
+        ldw<VW>(y + (long)(r + q * RG) * ldy + c, v[q]);
+        ldw<VW>(da + (long)(r + q * RG) * ldda + c, g[q]);
+      }
+#pragma unroll
+      for (int q = 0; q < RQ; ++q) step(r + q * RG, v[q], g[q]);
+    }
+    for (; r < r1; r += RG) {
+      f32x4 v[NV], g[NV];
+      ldw<VW>(y + (long)r * ldy + c, v);
+      ldw<VW>(da + (long)r * ldda + c, g);
+      step(r, v, g);
+    }
+  }
+  if (!RED) return;
+#pragma unroll
+  for (int j = 0; j < NV; ++j) {
+    red0[t * NV + j] = s0[j];
+    red1[t * NV + j] = s1[j];
+  }
+  __syncthreads();
+  // fixed-order tree over the RG row groups (deterministic)
+  int p2 = 1;
+  while (p2 < RG) p2 <<= 1;
+  for (int h = p2 >> 1; h > 0; h >>= 1) {
+    if (active && rg < h && rg + h < RG) {
+#pragma unroll
+      for (int j = 0; j < NV; ++j) {
+        red0[t * NV + j] += red0[(t + h * TC) * NV + j];
+        red1[t * NV + j] += red1[(t + h * TC) * NV + j];
+      }
+    }
+    __syncthreads();
+  }
+  if (rg == 0) {
+    float* p0 = part + (long)blockIdx.x * 2 * C;
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+      st4(p0 + c + 4 * j, red0[tc * NV + j]);
+      st4(p0 + C + c + 4 * j, red1[tc * NV + j]);
+    }
+  }
+}
+
 // Finalize kernels.  Sum the per-block partials (<= SEG_CHAN_MAXBLK rows:
 // chan_blocks) of one channel with one wave: lane l loads rows l, l+64, l+128, ... all at
 // once (one memory round trip; clamped index, masked add), sums them in that order in
@@ -257,6 +367,17 @@ __global__ void bn_bwd_finalize_kernel(const float* __restrict__ part, int nblk,
   coef[c] = (float)(g * inv);
   coef[C + c] = (float)(sdz / (double)M);
   coef[2 * C + c] = (float)(sdzx * inv * inv / (double)M);
+}
+
+// ... of bn_frozen_bwd_kernel's partials: dbeta = sum(dz), dgamma = sum(dz*(y - running_mean)) / sqrt(running_var + eps)
+__global__ void bn_frozen_finalize_kernel(const float* __restrict__ part, int nblk, int C,
+                                          const float* __restrict__ running_var, float eps, float* dgamma,
+                                          float* dbeta) {
+  int c;
+  double sdz, sdzx;
+  if (!sum_partials(part, nblk, C, C, &c, &sdz, &sdzx)) return;
+  if (dbeta) dbeta[c] = (float)sdz;
+  if (dgamma) dgamma[c] = (float)(sdzx * (1.0 / sqrt((double)running_var[c] + (double)eps)));
 }
 
 __global__ void colsum_finalize_kernel(const float* __restrict__ part, int nblk, int C, int ldp, float* out,
@@ -998,6 +1119,56 @@ SEG_API int seg_bn_eval_backward(const float* da, long ldda, const float* y, lon
   hipLaunchKernelGGL(bn_eval_bwd_kernel, dim3(ew_grid(M * (C / 4))), dim3(256), 0, stream, da, ldda, y, ldy, M, C,
                      scale, shift, act, dy, lddy);
   SEG_RET_LAST();
+}
+
+// Backward through a BatchNorm whose statistics are frozen (running_mean / running_var; scale, shift from
+// seg_bn_eval_coef), in one pass over dA and y: dy = scale * dz, dbeta = sum(dz), dgamma = sum(dz * (y -
+// running_mean)) / sqrt(running_var + eps).  dgamma == dbeta == NULL: the affine pair is frozen too, the elementwise
+// pass alone (seg_bn_eval_backward's result); dy == NULL: only the affine gradients.  `work` >=
+// seg_chan_workspace_floats(M, C) floats when an affine gradient is wanted.
+template <typename T>
+static int bn_frozen_backward_impl(const T* da, long ldda, const T* y, long ldy, long M, int C, const float* scale,
+                                   const float* shift, const float* running_mean, const float* running_var, float eps,
+                                   int act, float* dgamma, float* dbeta, float* work, T* dy, long lddy,
+                                   hipStream_t stream) {
+  if (C < 4 || (C & 3) || (ldy & 3) || (ldda & 3) || (lddy & 3) || M > 0x7fffffffL) return (int)hipErrorInvalidValue;
+  if (M < 1) return (int)hipSuccess;
+  const bool red = dgamma || dbeta;
+  if (!da || !y || !scale || !shift || (red && (!work || !running_mean || !running_var)))
+    return (int)hipErrorInvalidValue;
+  if (!red && !dy) return (int)hipSuccess;
+  const int nblk = chan_blocks(M);
+  const int rpb = seg_cdiv(M, nblk);
+  auto eoff8 = [](const T* p) { return ((uintptr_t)p / sizeof(T)) % 8 == 0; };
+  const bool v8 = C % 8 == 0 && ldy % 8 == 0 && ldda % 8 == 0 && eoff8(y) && eoff8(da) &&
+                  (!dy || (lddy % 8 == 0 && eoff8(dy)));
+  const dim3 grid(nblk, seg_cdiv(C / (v8 ? 8 : 4), kRedSlice));
+#define SEG_FROZEN_LAUNCH(VW, RED)                                                                                   \
+  hipLaunchKernelGGL((bn_frozen_bwd_kernel<T, VW, RED>), grid, dim3(kRedThreads), 0, stream, y, ldy, da, ldda, (int)M, \
+                     C, scale, shift, running_mean, act, work, dy, lddy, rpb)
+  if (v8 && red) SEG_FROZEN_LAUNCH(8, true);
+  else if (v8) SEG_FROZEN_LAUNCH(8, false);
+  else if (red) SEG_FROZEN_LAUNCH(4, true);
+  else SEG_FROZEN_LAUNCH(4, false);
+#undef SEG_FROZEN_LAUNCH
+  if (red)
+    hipLaunchKernelGGL(bn_frozen_finalize_kernel, dim3(seg_cdiv(C, 4)), dim3(256), 0, stream, work, nblk, C,
+                       running_var, eps, dgamma, dbeta);
+  SEG_RET_LAST();
+}
+SEG_API int seg_bn_frozen_backward(const float* da, long ldda, const float* y, long ldy, long M, int C,
+                                   const float* scale, const float* shift, const float* running_mean,
+                                   const float* running_var, float eps, int act, float* dgamma, float* dbeta,
+                                   float* work, float* dy, long lddy, hipStream_t stream) {
+  return bn_frozen_backward_impl(da, ldda, y, ldy, M, C, scale, shift, running_mean, running_var, eps, act, dgamma,
+                                 dbeta, work, dy, lddy, stream);
+}
+SEG_API int seg_bn_frozen_backward_bf16io(const __bf16* da, long ldda, const __bf16* y, long ldy, long M, int C,
+                                          const float* scale, const float* shift, const float* running_mean,
+                                          const float* running_var, float eps, int act, float* dgamma, float* dbeta,
+                                          float* work, __bf16* dy, long lddy, hipStream_t stream) {
+  return bn_frozen_backward_impl(da, ldda, y, ldy, M, C, scale, shift, running_mean, running_var, eps, act, dgamma,
+                                 dbeta, work, dy, lddy, stream);
 }
 
 // out[c] (+)= sum_r y[r][c]  -- conv bias gradient.  `work` >= seg_chan_workspace_floats.

@@ -8,6 +8,7 @@ Public surface (drop-in for the reference's src/unet.py and src/train.py):
     class_weights                         (nn.CrossEntropyLoss(weight=...) from pixel counts or a confusion matrix)
     Adam                                  (main.py:100's optimizer, one-launch HIP step)
     traceable                             (pure-torch CPU twin for convert.py's ONNX export)
+    freeze, unfreeze, frozen_modules      (fine-tuning: frozen backbone / frozen BatchNorm statistics)
     Predictor, preprocess_image           (inference.py's per-frame path)
     Overlay, overlay_predictions, COLOR_MAP
                                           (inference.py's overlay post-processing)
@@ -24,10 +25,11 @@ from .infer import Predictor, preprocess_image  # noqa: F401
 from .overlay import Overlay, overlay_predictions, COLOR_MAP  # noqa: F401
 from .optim import Adam  # noqa: F401
 from .export import traceable  # noqa: F401
+from .freeze import freeze, unfreeze, frozen_modules  # noqa: F401
 
 __all__ = ["MobileNetV2UNet", "UNet", "LightUNet", "double_conv", "inconv", "down", "up", "outconv",
            "train_model", "train_one_epoch", "validate", "summarize", "class_weights", "deterministic_init",
            "synthetic_batch",
            "CombinedLaneDataset", "DistributedWeightedSampler", "reference_sample_weights",
            "Predictor", "preprocess_image", "Overlay", "overlay_predictions", "COLOR_MAP",
-           "Adam", "traceable"]
+           "Adam", "traceable", "freeze", "unfreeze", "frozen_modules"]

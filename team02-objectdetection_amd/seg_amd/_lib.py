@@ -68,6 +68,7 @@ PROTOTYPES = {
     "seg_bn_apply": (_I, [_V, _L, _L, _I, _V, _V, _I, _V, _L, _V, _L, _V]),
     "seg_bn_backward": (_I, [_V, _L, _V, _L, _L, _I, _V, _V, _V, _V, _V, _I, _V, _V, _V, _V, _L, _V]),
     "seg_bn_eval_backward": (_I, [_V, _L, _V, _L, _L, _I, _V, _V, _I, _V, _L, _V]),
+    "seg_bn_frozen_backward": (_I, [_V, _L, _V, _L, _L, _I, _V, _V, _V, _V, _F, _I, _V, _V, _V, _V, _L, _V]),
     "seg_colsum": (_I, [_V, _L, _L, _I, _V, _V, _I, _V]),
     "seg_add": (_I, [_V, _L, _V, _L, _L, _I, _V, _L, _V]),
     "seg_upsample_fwd": (_I, [_V, _L, _I, _I, _I, _I, _V, _L, _I, _I, _I, _V]),
@@ -142,7 +143,8 @@ PROTOTYPES = {
     "seg_overlay_frame": (_I, [_V, _V, _I, _I, _V, _I, _I, _I, _I, _V, _V, _V, _V, _V, _L, _V]),
 }
 # bf16-storage variants: same C signature shape as their fp32 namesakes (pointers stay void*)
-for _n in ("seg_add", "seg_bn_stats", "seg_bn_apply", "seg_bn_backward", "seg_colsum", "seg_dw_fwd", "seg_dw_dgrad",
+for _n in ("seg_add", "seg_bn_stats", "seg_bn_apply", "seg_bn_backward", "seg_bn_frozen_backward", "seg_colsum",
+           "seg_dw_fwd", "seg_dw_dgrad",
            "seg_dw_wgrad", "seg_ce_upsample_loss", "seg_ce_upsample_grad", "seg_ce_upsample_eval", "seg_cew_upsample_loss",
            "seg_cew_upsample_grad", "seg_cew_upsample_eval", "seg_upsample_fwd",
            "seg_upsample_bwd", "seg_upsample_to_nchw", "seg_nchw_to_nhwc", "seg_maxpool2_fwd", "seg_maxpool2_bwd"):

@@ -59,6 +59,8 @@ class DataParallel(nn.Module):
         self._buckets = None
         self._slot = {}      # id(param) -> (bucket, offset)
         self._order = None
+        self._sig = None             # requires_grad of the program's parameters the buckets were planned for
+        self.generation = 0          # bumped when the buckets are planned anew (part of the engine's plan key)
         self._bn_flat = None
         self._replace_grads = False  # a bucket folded held .grad values in (see _launch)
         self._flag_sent = False      # this step's label count went out with the last bucket (label_flag)
@@ -126,11 +128,21 @@ class DataParallel(nn.Module):
         self._buckets = buckets
 
     def _ensure_plan(self, x):
-        if self._buckets is not None:
-            return
         from .engine import get_program
         N, _, H, W = x.shape
         prog = get_program(self.module, N, H, W)
+        sig = tuple(p.requires_grad for p in prog.params())
+        if self._buckets is not None and self._sig in (None, sig):  # None: plan_buckets called by hand
+            self._sig = sig
+            return
+        if self._buckets is not None:
+            # parameters were frozen or unfrozen (seg_amd.freeze): new buckets over the trainable ones.  The engine's
+            # plans carry the generation in their key, so no tape recorded against the old buckets is replayed.
+            for h in self._hooks or ():
+                h.remove()
+            self._hooks, self._slot, self._shadow = None, {}, None
+            self.generation += 1
+        self._sig = sig
         order, seen = [], set()
         for op in reversed(prog.ops):   # the engine's backward order
             for p in op.params():

@@ -19,6 +19,11 @@ order and accumulated by later ones; a residual (InvertedResidual
 `x + conv(x)`) hands its upstream gradient to the first writer of dx as a
 fused addend.
 
+Fine-tuning (seg_amd/freeze.py): each BatchNorm layer runs in its own module's mode -- train: batch statistics;
+eval: frozen on its running statistics, which it then leaves alone -- and the backward runs only what a parameter
+with requires_grad needs: grad_frontier() says per op whether it owes parameter gradients and whether anything
+upstream of its input trains.  Both patterns are part of a recorded plan's key (plan_signature).
+
 Routes: which kernel runs a conv is decided once per program and direction, in one
 place.  pick_routes() gives every ConvOp a Route for its forward, data gradient and
 weight gradient (op.route_f / route_d / route_w): the kernel family, the resolved C
@@ -281,11 +286,14 @@ class ConvOp:
     def forward(self, rt):
         s, y, i, r = rt.stream, self.y, self.inp, self.route_f
         stat = None
+        # this layer's BatchNorm mode, read once per recorded plan (its signature is part of the plan's key): batch
+        # statistics, or frozen on the running ones (seg_amd.freeze, model.eval())
+        train = rt.bn_train[id(self)] = self.bn is not None and self.bn.training
         if self.kind == "dw":
             rt.call(r.name, rt.ptr(i), i.ld, i.N, i.H, i.W, i.C, *self._in_xform(rt),
                     self.wk_f.data_ptr(), rt.ptr(y), y.ld, y.H, y.W, self.stride, s)
         else:
-            if self.bn is not None and rt.training:  # BN statistics fused into the conv epilogue, one row per tile
+            if train:  # BN statistics fused into the conv epilogue, one row per tile
                 ntiles, tile_rows = r.tiles
                 stat = rt.tmp(ntiles * 2 * self.cout)
             self._launch(rt, r, rt.ptr(i), i.ld, i, self.cin_pad, self.wk_f, rt.ptr(y), y, self.cout,
@@ -297,7 +305,7 @@ class ConvOp:
         bn, C, M = self.bn, self.cout, y.M
         st = torch.empty(4 * C, device=rt.device, dtype=torch.float32)
         mean, invstd, scale, shift = _stat_ptrs(st, C)
-        if rt.training:
+        if train:
             if bn.momentum is None:
                 raise NotImplementedError("BatchNorm2d(momentum=None) (cumulative average) is not supported")
             rm = bn.running_mean.data_ptr() if bn.track_running_stats else None
@@ -316,6 +324,8 @@ class ConvOp:
                         C, bn.weight.data_ptr(), bn.bias.data_ptr(), bn.eps, bn.momentum, rm, rv, nbt, mean, invstd,
                         scale, shift, *ws, s)
         else:
+            if bn.running_mean is None:
+                raise NotImplementedError("eval-mode BatchNorm2d without running statistics")
             rt.call("seg_bn_eval_coef", bn.weight.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr(),
                  bn.running_var.data_ptr(), bn.eps, C, scale, shift, s)
         rt.saved[id(self)] = st
@@ -376,10 +386,10 @@ class ConvOp:
         """BN-backward partials from this data gradient's epilogue (seg_conv_igemm_bnout*), when its output
         region is exactly the output of a train-mode BatchNorm layer P: the extra arguments, or None.  P's
         backward uses them if no other write reached the buffer afterwards (Run.wgen)."""
-        if not BNOUT or not rt.training:
+        if not BNOUT:
             return None
         p = rt.prog.bn_owner().get(i.key())
-        if p is None or id(p) not in rt.saved:
+        if p is None or id(p) not in rt.saved or not rt.bn_train[id(p)]:  # frozen statistics: no reduction to feed
             return None
         v = 16 // rt.es
         py = p.y
@@ -398,20 +408,42 @@ class ConvOp:
 
     def backward(self, rt):
         s, y = rt.stream, self.y
+        # grad_frontier: does anything upstream of the input / of the residual want this op's data gradient
+        _, dgrad, rgrad = rt.need[rt.cur_op]
+        dgrad = dgrad and not self.first
+        cw, cb = self.conv.weight, self.conv.bias
+        conv_grads = cw.requires_grad or (cb is not None and cb.requires_grad)
         dA = rt.grad_of(self.out)
         if self.bn is not None:
-            if not rt.training:
-                raise NotImplementedError("backward through eval-mode BatchNorm is not supported")
             C, M = self.cout, y.M
+            bn = self.bn
             st = rt.saved[id(self)]
             mean, invstd, scale, shift = _stat_ptrs(st, C)
-            g_w, g_b = rt.grad_param(self.bn.weight), rt.grad_param(self.bn.bias)
+            g_w = rt.grad_param(bn.weight) if bn.weight.requires_grad else None
+            g_b = rt.grad_param(bn.bias) if bn.bias.requires_grad else None
             # bench.py's "bn_bwd" family: algorithmic bytes of a BatchNorm backward = dA and y read once, dY written
             # once (3 |Y|), credited to the launch that writes dY
             abytes = 3 * M * C * rt.es
             bp = rt.bn_parts.pop(id(self), None)
-            dY = Act(rt.tmp_buf(M * r4(C)), 0, r4(C), C, y.N, y.H, y.W)
-            if bp is not None and bp[2] == rt.wgen.get(self.out.buf):
+            want_dy = dgrad or conv_grads  # else: only the affine gradients (nothing reads dY)
+            dY = Act(rt.tmp_buf(M * r4(C)), 0, r4(C), C, y.N, y.H, y.W) if want_dy else None
+            if not rt.bn_train[id(self)]:
+                # frozen statistics: one pass (seg_bn_frozen_backward), no reduction at all with a frozen affine pair
+                red = g_w is not None or g_b is not None
+                if red or want_dy:
+                    work = rt.tmp(query("seg_chan_workspace_floats", M, C)) if red else None
+                    rt.tcall("bn_bwd", abytes if want_dy else 0, rt.k("seg_bn_frozen_backward"), rt.gptr(dA), dA.ld,
+                             rt.ptr(y), y.ld, M, C, scale, shift, bn.running_mean.data_ptr(),
+                             bn.running_var.data_ptr(), bn.eps, self.act, g_w, g_b,
+                             work.data_ptr() if red else None, rt.ptr(dY) if want_dy else None,
+                             dY.ld if want_dy else 0, s)
+            elif not want_dy:
+                if g_w is not None or g_b is not None:  # the reduction half alone
+                    work = rt.tmp(query("seg_chan_workspace_floats", M, C) + 3 * C)
+                    rt.call(rt.k("seg_bn_bwd_coef"), rt.gptr(dA), dA.ld, rt.ptr(y), y.ld, M, C, bn.weight.data_ptr(),
+                            mean, invstd, scale, shift, self.act, g_w, g_b, work.data_ptr(),
+                            work.data_ptr() + 4 * query("seg_chan_workspace_floats", M, C), s)
+            elif bp is not None and bp[2] == rt.wgen.get(self.out.buf):
                 # the reduction's partials came out of the epilogue of the data gradient that completed dA (nothing
                 # wrote the buffer since): finalize them, then the apply
                 coef = rt.tmp(3 * C)
@@ -424,12 +456,20 @@ class ConvOp:
                 rt.tcall("bn_bwd", abytes, rt.k("seg_bn_backward"), rt.gptr(dA), dA.ld, rt.ptr(y), y.ld, M, C,
                          self.bn.weight.data_ptr(), mean, invstd, scale, shift, self.act,
                          g_w, g_b, work.data_ptr(), rt.ptr(dY), dY.ld, s)
-            if self.res is not None:
+            if self.res is not None and rgrad:
                 rt.add_pending(self.res, dA)
+            if dY is None:  # a frozen conv under a trainable BatchNorm affine pair, nothing trainable upstream
+                rt.params_done(self.params(), s)
+                return
         else:
             dY = dA
         dYp = rt.ptr(dY) if dY.buf.startswith("#") else rt.gptr(dY)
         M = y.M
+        if not conv_grads:  # a frozen conv: no side-stream work, only what is upstream of it
+            rt.params_done(self.params(), s)
+            if dgrad:
+                self._dgrad(rt, dY, dYp, s)
+            return
         # parameter gradients: on the side stream when overlapping (they only read dY and x,
         # and nothing on the main stream's data-gradient chain waits for them)
         # gradient tensors handed back to autograd are allocated on the main stream
@@ -437,7 +477,7 @@ class ConvOp:
         for p in (self.conv.weight, self.conv.bias):
             if p is not None and p.requires_grad:
                 rt.grad_param(p)
-        late = FORK_LATE and not self.first
+        late = FORK_LATE and dgrad
         if late:  # the data gradient first: the side stream's weight gradient then runs beside
             self._dgrad(rt, dY, dYp, s)  # the next layer's memory-bound BN backward, not this dgrad
         k = getattr(rt, "cur_op", -1)
@@ -459,7 +499,7 @@ class ConvOp:
             ctx, sw = rt.fork()
             with ctx:
                 self._param_grads(rt, dY, dYp, sw)
-        if not self.first and not late:
+        if dgrad and not late:
             self._dgrad(rt, dY, dYp, s)
 
     def _param_grads(self, rt, dY, dYp, s):
@@ -470,7 +510,7 @@ class ConvOp:
             rt.params_done(self.params(), s)  # diagnostics only: no conv weight / bias gradients (wrong training)
             return
         if self.conv.bias is not None and self.conv.bias.requires_grad:
-            if self.bn is not None and ZERO_BN_BIAS:
+            if self.bn is not None and ZERO_BN_BIAS and rt.bn_train[id(self)]:
                 # conv -> train-mode BatchNorm (src/unet.py:58-59,61-62): the bias shifts its whole channel by
                 # a constant that the batch mean removes again, so d loss / d bias = sum_p dY[p][c] = 0
                 # exactly (the reference computes that sum and gets fp32 rounding noise, ~1e-9 relative)
@@ -850,6 +890,44 @@ def pick_routes(prog: Program) -> None:
             op.route_w = _pick_wgrad(prog.math, op)
 
 
+def _frontier(prog: Program) -> list:
+    """Per op (parameter gradients, data gradient, residual gradient): see grad_frontier.  The third flag is the
+    same question as the second, asked of a ConvOp's residual input."""
+    wrote = []  # (buffer, first channel, end channel, something trainable at or upstream of the writer)
+
+    def upstream(a):
+        return a is not None and any(f for (b, lo, hi, f) in wrote if b == a.buf and lo < a.off + a.C and a.off < hi)
+
+    out = []
+    for op in prog.ops:
+        pg = any(p.requires_grad for p in op.params())
+        src = op.low if isinstance(op, UpsampleOp) else op.inp
+        dg, rg = upstream(src), upstream(getattr(op, "res", None))
+        o = op.out
+        wrote.append((o.buf, o.off, o.off + o.C, pg or dg or rg))
+        out.append((pg, dg, rg))
+    return out
+
+
+def grad_frontier(prog: Program) -> list:
+    """What the backward owes each op of `prog`: [(parameter gradients, data gradient)].  A pure function of the
+    program and its parameters' requires_grad flags (no tensor data, no device call).  `parameter gradients`: one of
+    the op's own parameters requires a gradient.  `data gradient`: some op upstream of this op's input has such a
+    parameter -- transitively, through concat slices (a reader of the whole buffer is downstream of every slice's
+    writer), residuals, pools and upsamples.  The backward skips an op with neither, runs no data gradient (nor a
+    BatchNorm layer's dY, if its conv wants no gradient either) for an op without the second, and feeds a residual
+    only where something upstream of it trains."""
+    return [(pg, dg) for pg, dg, _ in _frontier(prog)]
+
+
+def plan_signature(prog: Program) -> tuple:
+    """What a recorded plan bakes in besides the shapes: each BatchNorm layer's mode (batch or running statistics)
+    and each parameter's requires_grad (the gradient frontier, the flat gradient slots).  Part of the plan's key, so
+    freezing or unfreezing between steps records (or finds again) the plan for that pattern."""
+    return (tuple(op.bn.training for op in prog.ops if isinstance(op, ConvOp) and op.bn is not None),
+            tuple(p.requires_grad for p in prog.params()))
+
+
 def _pick_conv(math, op, d):
     """Route of a dense conv's forward (d = 0: x [M][K = cin_pad] -> y [M][C = Cout]) or data gradient (d = 1: the
     transposed conv, dY [M][K = r4(Cout)] -> dx [M][C = Cin]).  Precedence: thin-K 1x1, Winograd (f32), LDS halo (f32:
@@ -1105,6 +1183,8 @@ class Run:
         self.bufs = {n: torch.empty(rows * ld, device=self.device, dtype=self.store)
                      for n, (rows, ld) in prog.bufs.items()}
         self.saved = {}
+        self.bn_train = {}    # id(op) -> its BatchNorm ran on batch statistics (ConvOp.forward; False: frozen / none)
+        self.need = None      # _frontier(prog), taken when the backward starts
         self.bn_parts = {}    # id(op) -> [tile partials, tiles, write generation]: its BN-backward reduction from
                               # the epilogue of the data gradient that completed its dA (seg_conv_igemm_bnout*)
         self.wgen = {}        # gradient buffer name -> write generation (every write to the buffer bumps it)
@@ -1403,11 +1483,14 @@ class Run:
             self.main = torch.cuda.current_stream(self.device)
             self.side = _side_stream(self.device)
             self._side_ctx = torch.cuda.StreamContext(self.side)  # re-entered by every fork
+        self.need = _frontier(self.prog)
         try:
             for k in range(len(self.prog.ops) - 1, -1, -1):
                 self.cur_op = k
                 if self.defer is not None and k == self.defer[1]:
                     self.flush_deferred()
+                if not any(self.need[k]):  # behind the gradient frontier: nothing here or upstream trains
+                    continue
                 if self.rec is not None:
                     self.rec.label = f"{k}:bwd"
                 self.prog.ops[k].backward(self)
@@ -1824,8 +1907,10 @@ def _plan(model, prog, mode, ignore_index, sync, needs_grad, device, opts=(None,
     pointer is patched into the tapes per replay, so new weight values or a new weight tensor need no new plan."""
     cache = model.__dict__.setdefault("_segamd_plans", {})
     weight, eps, reduction = opts
-    key = (id(prog), mode, model.training, ignore_index, id(sync) if sync is not None else None, needs_grad, OVERLAP,
-           (eps, reduction, weight is None))
+    # a DataParallel wrapper re-plans its buckets when the requires_grad pattern changes (its generation): the tapes
+    # of an earlier generation point into buckets that are gone
+    key = (id(prog), mode, model.training, ignore_index, (id(sync), sync.generation) if sync is not None else None,
+           needs_grad, OVERLAP, (eps, reduction, weight is None), plan_signature(prog))
     fp = _fingerprint(prog)
     plan = cache.pop(key, None)  # re-inserted below: dict order = least recently used first
     if plan is None or plan.sync is not sync or plan.fp != fp:

@@ -139,4 +139,14 @@ def traceable(model: nn.Module) -> nn.Module:
     else:
         raise TypeError(f"no traceable twin for {type(model).__name__}")
     twin.load_state_dict({k: v.detach().cpu() for k, v in model.state_dict().items()})
-    return twin.train(model.training)
+    # ... and the same fine-tuning state: requires_grad per parameter, train / eval per module, seg_amd.freeze's book
+    src = dict(model.named_parameters())
+    for n, p in twin.named_parameters():
+        p.requires_grad_(src[n].requires_grad)
+    twin.train(model.training)
+    mods = dict(model.named_modules())
+    for n, m in twin.named_modules():
+        m.training = mods[n].training
+    if "_segamd_frozen" in model.__dict__:
+        twin.__dict__["_segamd_frozen"] = {n: dict(f) for n, f in model.__dict__["_segamd_frozen"].items()}
+    return twin

@@ -235,13 +235,32 @@ def validate(model, val_loader, criterion, device, progress: bool = True, epoch:
 
 def train_model(model, train_loader, criterion, optimizer, device, epochs=10,
                 checkpoint_pattern: str | None = "Models/obj/obj_MOB_1_epoch_{epoch}.pth", progress: bool = True,
-                augment=None, val_loader=None, best_checkpoint: str | None = None):
+                augment=None, val_loader=None, best_checkpoint: str | None = None, freeze=None,
+                freeze_epochs: int | None = None):
     """Train for `epochs` epochs (src/train.py:6-79).  With `val_loader`, each epoch ends with the
     reference's validation phase (commented out there, src/train.py:46-76): validate(), the
     epoch's result lines, and on an improved validation loss a state_dict at `best_checkpoint`
-    (when given).  Without it, output and files are the reference's as it stands."""
+    (when given).  Without it, output and files are the reference's as it stands.
+
+    freeze: what seg_amd.freeze takes ("backbone", a module, a list of either) -- frozen (parameters and
+    BatchNorm statistics) before the first epoch; freeze_epochs=K unfreezes it before epoch K+1, None keeps it
+    frozen for the whole run.  One line is printed at each change; without `freeze` nothing changes."""
+    from .freeze import freeze as _freeze, unfreeze as _unfreeze
+    if freeze is not None:
+        if isinstance(freeze, (str, nn.Module)):
+            freeze = [freeze]
+        freeze = list(freeze)
+        _freeze(model, freeze)
+        if _is_rank0():
+            names = ", ".join(f if isinstance(f, str) else type(f).__name__ for f in freeze)
+            until = "the whole run" if freeze_epochs is None else f"{freeze_epochs} epoch(s)"
+            print(f"Frozen for {until}: {names} (parameters and BatchNorm statistics)")
     best_val_loss = float("inf")  # stays inf without a val_loader, as in the reference (src/train.py:46-76)
     for epoch in range(epochs):
+        if freeze is not None and freeze_epochs is not None and epoch == freeze_epochs:
+            _unfreeze(model, freeze)
+            if _is_rank0():
+                print(f"Unfrozen before epoch {epoch + 1}: {names}")
         sampler = getattr(train_loader, "sampler", None)
         if hasattr(sampler, "set_epoch"):
             sampler.set_epoch(epoch)  # DistributedWeightedSampler: a new shared draw per epoch

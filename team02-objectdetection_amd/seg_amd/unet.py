@@ -73,6 +73,14 @@ class _SegModel(nn.Module):
     on this module's parameters (seg_amd.export.torch_forward), so train_model, Adam and
     state_dict work there too; the product never selects it for GPU input."""
 
+    def train(self, mode: bool = True):
+        """nn.Module.train, after which the BatchNorm layers frozen by seg_amd.freeze(bn_stats=True) are back in
+        eval mode: a training loop's model.train() keeps the freeze."""
+        super().train(mode)
+        from .freeze import keep_frozen
+        keep_frozen(self)
+        return self
+
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if x.device.type == "cpu":
             from .export import torch_forward
