@@ -606,6 +606,43 @@ int seg_adam_step_skip(const SegAdamTensor* tensors, const long* chunks, int nch
                        float one_minus_beta1, float beta2, float one_minus_beta2, float eps, const float* skip,
                        hipStream_t stream);
 
+/* ---- AdamW and global-norm gradient clipping over the same chunk map ----------
+ * The tensor table of these entry points is a device array of 56-byte records,
+ * passed as const void*:
+ *   struct SegAdamWTensor {
+ *     float* p; const float* g; float* m; float* v;   exp_avg, exp_avg_sq as above
+ *     long n;
+ *     float step_size;   -lr / (1 - beta1^t)
+ *     float bc2_sqrt;    sqrt(1 - beta2^t)
+ *     float decay;       (float)(1 - lr * weight_decay), formed in double
+ *     float pad;
+ *   };
+ * seg_grad_sumsq and seg_grad_scale read only g and n of each record. */
+/* torch's foreach AdamW (decoupled_weight_decay) per element, fp32, in its order:
+ *   g *= *grad_scale; p *= decay; then the Adam arithmetic of seg_adam_step.
+ * Both products are rounded on their own, so decay == 1 with grad_scale == NULL is
+ * bit for bit seg_adam_step_skip, and a grad_scale is bit for bit seg_grad_scale
+ * followed by the unscaled step.  skip: as seg_adam_step_skip.  grad_scale: one
+ * device float (NULL = 1), e.g. out + 1 of seg_grad_sumsq; .grad is not written. */
+int seg_adamw_step(const void* tensors, const long* chunks, int nchunks, int chunk,
+                   float one_minus_beta1, float beta2, float one_minus_beta2, float eps, const float* skip,
+                   const float* grad_scale, hipStream_t stream);
+/* floats of workspace seg_grad_sumsq needs for nchunks chunks */
+long seg_grad_norm_workspace_floats(int nchunks);
+/* Global L2 norm of every gradient in the table: one partial sum of squares per
+ * chunk into `work`, then a one-block launch that adds the partials in a fixed
+ * order (no atomics: bitwise the same on every run) and writes
+ *   out[0] = norm,
+ *   out[1] = min(max_norm / (norm + 1e-6), 1)  (torch.nn.utils.clip_grad_norm_'s
+ *            coefficient; NaN for a NaN norm; 1 when max_norm <= 0 or infinite),
+ *   out[2] = 1 if the norm is inf or NaN, else 0. */
+int seg_grad_sumsq(const void* tensors, const long* chunks, int nchunks, int chunk, float max_norm,
+                   float* work, float* out, hipStream_t stream);
+/* g *= *scale in place (scale: one device float); when *scale == 1 the kernel
+ * returns without touching memory.  For optimizers without a fused grad_scale. */
+int seg_grad_scale(const void* tensors, const long* chunks, int nchunks, int chunk, const float* scale,
+                   hipStream_t stream);
+
 /* ---- launch tape (csrc/tape.hip): a recorded sequence of the launches above,
  *      replayed by one host call per segment -- the engine's training step
  *      (seg_amd/tape.py) without ~600 per-launch ctypes calls.  Not a hipGraph:

@@ -16,6 +16,9 @@
 // Work split: a host-built chunk map (tensor index, first element) of at most
 // `chunk` elements each; one 256-thread block per chunk.  Parameters with no
 // gradient (the unused classifier) are simply absent from the table.
+//
+// AdamW and gradient clipping (seg_adamw_step, seg_grad_sumsq, seg_grad_scale) run over the
+// same chunk map with a wider record, SegAdamWTensor; see the second half of this file.
 #include "common.h"
 
 struct SegAdamTensor {  // 48 bytes, the layout seg_amd/optim.py packs
@@ -69,4 +72,163 @@ SEG_API int seg_adam_step(const SegAdamTensor* tensors, const long* chunks, int 
                           float one_minus_beta1, float beta2, float one_minus_beta2, float eps, hipStream_t stream) {
   return seg_adam_step_skip(tensors, chunks, nchunks, chunk, one_minus_beta1, beta2, one_minus_beta2, eps, nullptr,
                             stream);
+}
+
+// ---- AdamW, global-norm clipping -------------------------------------------------------
+//
+// seg_adamw_step: torch's foreach AdamW (torch/optim/adam.py::_multi_tensor_adam with
+// decoupled_weight_decay=True), the Adam arithmetic above with two more fp32 multiplies:
+//   g = g * (*grad_scale)                  the clip coefficient, applied as the gradient is loaded
+//   p = p * decay                          _foreach_mul_(params, 1 - lr * weight_decay)
+// Both are rounded products of their own (mul_rn: never contracted into the add that
+// follows), so decay == 1 and no grad_scale is bit for bit seg_adam_step_skip, and a fused
+// grad_scale is bit for bit seg_grad_scale followed by the unscaled step.  Multiplying by
+// exactly 1.f changes no value, so neither multiply needs a branch.
+//
+// seg_grad_sumsq: the global L2 norm of every gradient in the table.  One block per chunk
+// writes its sum of squares to part[block]; a second, one-block launch adds the partials in
+// a fixed order (in double) and writes out[0..2].  No atomics: the result is the same bit
+// pattern on every run.  The second launch instead of a last-block-done ticket: it needs no
+// zeroed counter in the workspace and no cross-XCD hand-off, and its cost is one kernel
+// boundary.
+struct SegAdamWTensor {  // 56 bytes, the layout seg_amd/optim.py packs (_pack_w)
+  float* p;
+  const float* g;
+  float* m;
+  float* v;
+  long n;
+  float step_size;  // -lr / bc1
+  float bc2_sqrt;   // sqrt(1 - b2^t)
+  float decay;      // float(1 - lr * weight_decay)
+  float pad;
+};
+
+namespace {
+
+// a * b rounded to fp32 by itself: the empty asm hides the product from the contraction pass
+__device__ __forceinline__ float mul_rn(float a, float b) {
+  float r = a * b;
+  asm("" : "+v"(r));
+  return r;
+}
+
+__global__ __launch_bounds__(256) void adamw_kernel(const SegAdamWTensor* __restrict__ ts,
+                                                    const long* __restrict__ chunks, int chunk, float w, float b2,
+                                                    float cv, float eps, const float* __restrict__ skip,
+                                                    const float* __restrict__ grad_scale) {
+  if (skip && *skip != 0.f) return;
+  const float gs = grad_scale ? *grad_scale : 1.f;
+  const long ti = chunks[2 * blockIdx.x], start = chunks[2 * blockIdx.x + 1];
+  const SegAdamWTensor t = ts[ti];
+  const long end = std::min<long>(t.n, start + chunk);
+  for (long i = start + threadIdx.x; i < end; i += 256) {
+    const float g = mul_rn(t.g[i], gs);
+    float m = t.m[i], v = t.v[i];
+    const float p = mul_rn(t.p[i], t.decay);
+    m = m + w * (g - m);
+    v = v * b2;
+    v = v + cv * g * g;
+    const float d = sqrtf(v) / t.bc2_sqrt + eps;
+    t.p[i] = p + t.step_size * (m / d);
+    t.m[i] = m;
+    t.v[i] = v;
+  }
+}
+
+// part[block] = sum of g^2 over the block's chunk: per thread a serial fma chain over its
+// <= chunk / 256 elements, then the 6-level wave butterfly and a 2-level sum of the 4 waves.
+__global__ __launch_bounds__(256) void grad_sumsq_kernel(const SegAdamWTensor* __restrict__ ts,
+                                                         const long* __restrict__ chunks, int chunk,
+                                                         float* __restrict__ part) {
+  __shared__ float ws[4];
+  const long ti = chunks[2 * blockIdx.x], start = chunks[2 * blockIdx.x + 1];
+  const float* __restrict__ g = ts[ti].g;
+  const long end = std::min<long>(ts[ti].n, start + chunk);
+  float acc = 0.f;
+  for (long i = start + threadIdx.x; i < end; i += 256) {
+    const float x = g[i];
+    acc = fmaf(x, x, acc);
+  }
+  acc = wave_sum(acc);
+  if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) part[blockIdx.x] = (ws[0] + ws[1]) + (ws[2] + ws[3]);
+}
+
+// One block: thread t adds part[t], part[t + 256], ... in double, then a fixed tree over the 256 sums.
+__global__ __launch_bounds__(256) void grad_norm_finalize_kernel(const float* __restrict__ part, int n,
+                                                                 float max_norm, float* __restrict__ out) {
+  __shared__ double s[256];
+  double acc = 0.0;
+  for (int i = threadIdx.x; i < n; i += 256) acc += (double)part[i];
+  s[threadIdx.x] = acc;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) s[threadIdx.x] += s[threadIdx.x + o];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    const float norm = (float)sqrt(s[0]);
+    float coef = 1.f;
+    if (max_norm > 0.f && max_norm < __builtin_inff()) {
+      coef = max_norm / (norm + 1e-6f);  // torch.nn.utils.clip_grads_with_norm_
+      coef = coef > 1.f ? 1.f : coef;    // clamp(max=1): a NaN stays a NaN
+    }
+    out[0] = norm;
+    out[1] = coef;
+    out[2] = (norm == norm && norm != __builtin_inff()) ? 0.f : 1.f;
+  }
+}
+
+__global__ __launch_bounds__(256) void grad_scale_kernel(const SegAdamWTensor* __restrict__ ts,
+                                                         const long* __restrict__ chunks, int chunk,
+                                                         const float* __restrict__ scale) {
+  const float s = *scale;
+  if (s == 1.f) return;  // nothing was clipped: the gradients stay as they are, untouched
+  const long ti = chunks[2 * blockIdx.x], start = chunks[2 * blockIdx.x + 1];
+  float* __restrict__ g = const_cast<float*>(ts[ti].g);
+  const long end = std::min<long>(ts[ti].n, start + chunk);
+  for (long i = start + threadIdx.x; i < end; i += 256) g[i] = g[i] * s;
+}
+
+}  // namespace
+
+// tensors: device array of SegAdamWTensor (passed as const void*: include/segamd.h documents the
+// record); chunks / nchunks / chunk and the four scalars as seg_adam_step_skip.  skip: as there.
+// grad_scale: one device float every gradient element is multiplied by as it is loaded (NULL = 1);
+// .grad itself is not written.
+SEG_API int seg_adamw_step(const void* tensors, const long* chunks, int nchunks, int chunk, float one_minus_beta1,
+                           float beta2, float one_minus_beta2, float eps, const float* skip, const float* grad_scale,
+                           hipStream_t stream) {
+  if (nchunks < 0 || chunk < 1) return (int)hipErrorInvalidValue;
+  if (nchunks == 0) return (int)hipSuccess;
+  hipLaunchKernelGGL(adamw_kernel, dim3(nchunks), dim3(256), 0, stream, (const SegAdamWTensor*)tensors, chunks, chunk,
+                     one_minus_beta1, beta2, one_minus_beta2, eps, skip, grad_scale);
+  SEG_RET_LAST();
+}
+
+// Floats of workspace seg_grad_sumsq needs: one partial per chunk.
+SEG_API long seg_grad_norm_workspace_floats(int nchunks) { return nchunks > 0 ? (long)nchunks : 0; }
+
+// out[0] = sqrt(sum g^2) over the table (only g and n of each record are read);
+// out[1] = min(max_norm / (out[0] + 1e-6), 1), or 1 when max_norm <= 0 or infinite; NaN when the norm is NaN;
+// out[2] = 1 if the norm is inf or NaN, else 0.  work: seg_grad_norm_workspace_floats(nchunks) floats.
+SEG_API int seg_grad_sumsq(const void* tensors, const long* chunks, int nchunks, int chunk, float max_norm,
+                           float* work, float* out, hipStream_t stream) {
+  if (nchunks < 0 || chunk < 1) return (int)hipErrorInvalidValue;
+  if (nchunks == 0) return (int)hipSuccess;
+  hipLaunchKernelGGL(grad_sumsq_kernel, dim3(nchunks), dim3(256), 0, stream, (const SegAdamWTensor*)tensors, chunks,
+                     chunk, work);
+  hipLaunchKernelGGL(grad_norm_finalize_kernel, dim3(1), dim3(256), 0, stream, work, nchunks, max_norm, out);
+  SEG_RET_LAST();
+}
+
+// g *= *scale in place over the table (only g and n are read); returns at once on the device when *scale == 1.
+SEG_API int seg_grad_scale(const void* tensors, const long* chunks, int nchunks, int chunk, const float* scale,
+                           hipStream_t stream) {
+  if (nchunks < 0 || chunk < 1) return (int)hipErrorInvalidValue;
+  if (nchunks == 0) return (int)hipSuccess;
+  hipLaunchKernelGGL(grad_scale_kernel, dim3(nchunks), dim3(256), 0, stream, (const SegAdamWTensor*)tensors, chunks,
+                     chunk, scale);
+  SEG_RET_LAST();
 }

@@ -7,6 +7,8 @@ Public surface (drop-in for the reference's src/unet.py and src/train.py):
     validate, summarize                   (validation loss, per-class IoU, mIoU: one fused pass per batch)
     class_weights                         (nn.CrossEntropyLoss(weight=...) from pixel counts or a confusion matrix)
     Adam                                  (main.py:100's optimizer, one-launch HIP step)
+    AdamW, decay_groups                   (torch.optim.AdamW as a one-launch HIP step; decayed / undecayed groups)
+    grad_norm, clip_grad_norm_            (global L2 gradient norm and clipping on the device)
     traceable                             (pure-torch CPU twin for convert.py's ONNX export)
     freeze, unfreeze, frozen_modules      (fine-tuning: frozen backbone / frozen BatchNorm statistics)
     Predictor, preprocess_image           (inference.py's per-frame path)
@@ -23,7 +25,7 @@ from .detinit import deterministic_init, synthetic_batch  # noqa: F401
 from .data import CombinedLaneDataset, DistributedWeightedSampler, reference_sample_weights  # noqa: F401
 from .infer import Predictor, preprocess_image  # noqa: F401
 from .overlay import Overlay, overlay_predictions, COLOR_MAP  # noqa: F401
-from .optim import Adam  # noqa: F401
+from .optim import Adam, AdamW, clip_grad_norm_, decay_groups, grad_norm  # noqa: F401
 from .export import traceable  # noqa: F401
 from .freeze import freeze, unfreeze, frozen_modules  # noqa: F401
 
@@ -32,4 +34,5 @@ __all__ = ["MobileNetV2UNet", "UNet", "LightUNet", "double_conv", "inconv", "dow
            "synthetic_batch",
            "CombinedLaneDataset", "DistributedWeightedSampler", "reference_sample_weights",
            "Predictor", "preprocess_image", "Overlay", "overlay_predictions", "COLOR_MAP",
-           "Adam", "traceable", "freeze", "unfreeze", "frozen_modules"]
+           "Adam", "AdamW", "clip_grad_norm_", "decay_groups", "grad_norm",
+           "traceable", "freeze", "unfreeze", "frozen_modules"]

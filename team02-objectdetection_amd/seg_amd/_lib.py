@@ -91,6 +91,10 @@ PROTOTYPES = {
     "seg_augment": (_I, [_V, _V, _I, _I, _I, _V, _F, _F, _F, _F, _F, _F, _V, _V, _V]),
     "seg_adam_step": (_I, [_V, _V, _I, _I, _F, _F, _F, _F, _V]),
     "seg_adam_step_skip": (_I, [_V, _V, _I, _I, _F, _F, _F, _F, _V, _V]),
+    "seg_adamw_step": (_I, [_V, _V, _I, _I, _F, _F, _F, _F, _V, _V, _V]),
+    "seg_grad_norm_workspace_floats": (_L, [_I]),
+    "seg_grad_sumsq": (_I, [_V, _V, _I, _I, _F, _V, _V, _V]),
+    "seg_grad_scale": (_I, [_V, _V, _I, _I, _V, _V]),
     # launch tape (csrc/tape.hip, seg_amd/tape.py)
     "seg_tape_fn_index": (_I, [ctypes.c_char_p]),
     "seg_tape_fn_nargs": (_I, [_I]),

@@ -1,6 +1,6 @@
-"""Adam with a one-launch HIP step (csrc/adam.hip, seg_adam_step).
+"""Adam and AdamW with a one-launch HIP step, and global-norm gradient clipping (csrc/adam.hip).
 
-Drop-in for the reference's `optim.Adam(model.parameters(), lr=1.5e-4)` (main.py:100),
+`Adam` is the drop-in for the reference's `optim.Adam(model.parameters(), lr=1.5e-4)` (main.py:100),
 stepped once per batch by train_model (src/train.py:39): same constructor, same
 param_groups and state_dict layout (state 'step' as a CPU tensor, 'exp_avg',
 'exp_avg_sq'), so checkpoints move between the two.  torch's foreach Adam issues ~8
@@ -9,19 +9,41 @@ again; seg_adam_step reads and writes each element once with the same fp32 opera
 order (see adam.hip).  Supported: the reference's configuration (no weight decay, no
 amsgrad, not maximize) on CUDA fp32 dense tensors; anything else raises -- there is no
 silent fallback.
+
+`AdamW` is the same for `torch.optim.AdamW` (decoupled weight decay): one seg_adamw_step launch per
+parameter group, torch's `_multi_tensor_adam` arithmetic with `p *= 1 - lr * weight_decay` in front; per-group
+lr / betas / eps / weight_decay, lr read at every step (torch.optim.lr_scheduler.* work unchanged).  Weight decay
+stays refused by `Adam` (its L2 form, added to the gradient, is not implemented), as do amsgrad, maximize,
+capturable and differentiable by both.
+
+Clipping: `grad_norm` (the global L2 norm, the clip coefficient and a non-finite flag, on the device, no host
+wait), `clip_grad_norm_` (torch.nn.utils.clip_grad_norm_'s contract, L2 only) and `step(grad_scale=...)`, which
+multiplies each gradient element by a device float as the step loads it -- `.grad` is never rewritten.
+`decay_groups` builds the usual two parameter groups (weights decayed, biases and BatchNorm not).
 """
 from __future__ import annotations
 
 import torch
+from torch import nn
 
-from ._lib import call
+from ._lib import call, query
 
 _CHUNK = 4096  # elements per block
+_CHUNK_MAPS = {}  # (sizes, device) -> chunk map, for the functions that have no optimizer to keep it
 
 
-class Adam(torch.optim.Adam):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, **kw):
-        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, **kw)
+def _chunk_map(sizes, device):
+    """Device int64 [(tensor index, first element)] pairs covering every tensor in pieces of <= _CHUNK elements."""
+    pairs = [(ti, s) for ti, n in enumerate(sizes) for s in range(0, n, _CHUNK)]
+    return torch.tensor(pairs, dtype=torch.int64).reshape(-1, 2).to(device)
+
+
+class _OneLaunchStep:
+    """The host side of Adam and AdamW: argument checks, state, CPU step counters, the tensor table and the launch.
+    _DECOUPLED: the class applies weight decay (AdamW's form); otherwise any weight decay is refused."""
+    _DECOUPLED = False
+
+    def _init_one_launch(self):
         self._chunk_maps = {}
         self._last_steps = []  # the CPU step counters the last step() advanced (undo_step_count)
 
@@ -29,31 +51,36 @@ class Adam(torch.optim.Adam):
         key = (tuple(sizes), device)
         cm = self._chunk_maps.get(key)
         if cm is None:
-            pairs = [(ti, s) for ti, n in enumerate(sizes) for s in range(0, n, _CHUNK)]
-            cm = torch.tensor(pairs, dtype=torch.int64).reshape(-1, 2).to(device)
-            self._chunk_maps[key] = cm
+            cm = self._chunk_maps[key] = _chunk_map(sizes, device)
         return cm
 
     @torch.no_grad()
-    def step(self, closure=None, *, skip_if_nonzero: torch.Tensor | None = None):
-        """One Adam step.  skip_if_nonzero: a one-element fp32 device tensor; when it holds a non-zero value at the
+    def step(self, closure=None, *, skip_if_nonzero: torch.Tensor | None = None,
+             grad_scale: torch.Tensor | None = None):
+        """One step.  skip_if_nonzero: a one-element fp32 device tensor; when it holds a non-zero value at the
         time the step runs on the GPU (stream order), the kernel leaves every parameter and moment unchanged --
         train_one_epoch passes the batch's out-of-range label count here so the step can be queued without a host
         wait; the CPU step counters advance at queue time, and the loop calls undo_step_count() before it raises, so
-        a skipped step leaves 'step' where the reference's (which never reaches optimizer.step()) leaves it."""
+        a skipped step leaves 'step' where the reference's (which never reaches optimizer.step()) leaves it.
+        grad_scale: a one-element fp32 device tensor (grad_norm(...)[1:2]); every gradient element is multiplied by
+        it as it is loaded, bit for bit as if the gradients had been scaled in place first; .grad is not written."""
+        name = type(self).__name__
         loss = None
-        if skip_if_nonzero is not None and not (skip_if_nonzero.is_cuda and skip_if_nonzero.dtype == torch.float32
-                                                and skip_if_nonzero.numel() >= 1):
-            raise ValueError("skip_if_nonzero must be a float32 CUDA tensor")
+        for what, t in (("skip_if_nonzero", skip_if_nonzero), ("grad_scale", grad_scale)):
+            if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.numel() >= 1):
+                raise ValueError(f"{what} must be a float32 CUDA tensor")
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
         self._last_steps = []
+        wide = self._DECOUPLED or grad_scale is not None  # seg_adamw_step; else seg_adam_step_skip, as ever
         for group in self.param_groups:
-            if group["weight_decay"] != 0 or group["amsgrad"] or group["maximize"] or group.get("capturable") \
-                    or group.get("differentiable") or group.get("decoupled_weight_decay"):
-                raise NotImplementedError("seg_amd.Adam supports the reference's configuration only "
-                                          "(weight_decay=0, amsgrad/maximize/capturable/differentiable off)")
+            if group["amsgrad"] or group["maximize"] or group.get("capturable") or group.get("differentiable") \
+                    or (not self._DECOUPLED and (group["weight_decay"] != 0 or group.get("decoupled_weight_decay"))):
+                raise NotImplementedError(
+                    f"seg_amd.{name} supports " + ("decoupled weight decay" if self._DECOUPLED else
+                                                   "the reference's configuration (weight_decay=0)")
+                    + " with amsgrad/maximize/capturable/differentiable off only")
             b1, b2 = group["betas"]
             lr, eps = float(group["lr"]), group["eps"]
             ps = [p for p in group["params"] if p.grad is not None]
@@ -63,7 +90,7 @@ class Adam(torch.optim.Adam):
                 g = p.grad
                 if not (p.is_cuda and p.dtype == torch.float32 and g.dtype == torch.float32 and not g.is_sparse
                         and p.is_contiguous() and g.is_contiguous()):
-                    raise NotImplementedError("seg_amd.Adam needs contiguous fp32 CUDA parameters and gradients")
+                    raise NotImplementedError(f"seg_amd.{name} needs contiguous fp32 CUDA parameters and gradients")
                 st = self.state[p]
                 if len(st) == 0:
                     st["step"] = torch.tensor(0.0)
@@ -78,12 +105,20 @@ class Adam(torch.optim.Adam):
                 bc1, bc2 = 1 - b1 ** t, 1 - b2 ** t
                 rows.append((p.data_ptr(), p.grad.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(),
                              p.numel(), -(lr / bc1), bc2 ** 0.5))
+            if wide:  # + (decay, pad)
+                tail = (1 - lr * group["weight_decay"] if self._DECOUPLED else 1.0, 0.0)
+                rows = [r + tail for r in rows]
             device = ps[0].device
-            table = _pack(rows).pin_memory().to(device, non_blocking=True)
+            table = (_pack_w(rows) if wide else _pack(rows)).pin_memory().to(device, non_blocking=True)
             chunks = self._chunks([p.numel() for p in ps], device)
-            call("seg_adam_step_skip", table.data_ptr(), chunks.data_ptr(), chunks.shape[0], _CHUNK, 1 - b1, b2, 1 - b2,
-                 eps, skip_if_nonzero.data_ptr() if skip_if_nonzero is not None else None,
-                 torch.cuda.current_stream(device).cuda_stream)
+            skip = skip_if_nonzero.data_ptr() if skip_if_nonzero is not None else None
+            stream = torch.cuda.current_stream(device).cuda_stream
+            if wide:
+                call("seg_adamw_step", table.data_ptr(), chunks.data_ptr(), chunks.shape[0], _CHUNK, 1 - b1, b2,
+                     1 - b2, eps, skip, grad_scale.data_ptr() if grad_scale is not None else None, stream)
+            else:
+                call("seg_adam_step_skip", table.data_ptr(), chunks.data_ptr(), chunks.shape[0], _CHUNK, 1 - b1, b2,
+                     1 - b2, eps, skip, stream)
         return loss
 
     def undo_step_count(self):
@@ -96,8 +131,120 @@ class Adam(torch.optim.Adam):
         self._last_steps = []
 
 
+class Adam(_OneLaunchStep, torch.optim.Adam):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, **kw):
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, **kw)
+        self._init_one_launch()
+
+
+class AdamW(_OneLaunchStep, torch.optim.AdamW):
+    """torch.optim.AdamW with one seg_adamw_step launch per parameter group (module docstring)."""
+    _DECOUPLED = True
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False, **kw):
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, **kw)
+        self._init_one_launch()
+
+
 def _pack(rows):
     """SegAdamTensor[] (include/segamd.h) as int64 words: 4 pointers, n, (step_size, bc2_sqrt)."""
     f = torch.tensor([[r[5], r[6]] for r in rows], dtype=torch.float32)
     words = torch.tensor([r[:5] for r in rows], dtype=torch.int64)
     return torch.cat([words, f.view(torch.int64)], dim=1).contiguous()
+
+
+def _pack_w(rows):
+    """SegAdamWTensor[] (include/segamd.h) as int64 words: 4 pointers, n, (step_size, bc2_sqrt), (decay, pad)."""
+    f = torch.tensor([r[5:9] for r in rows], dtype=torch.float32)
+    words = torch.tensor([r[:5] for r in rows], dtype=torch.int64)
+    return torch.cat([words, f.view(torch.int64)], dim=1).contiguous()
+
+
+# ------------------------------------------------------------------ gradient norm and clipping
+
+def _with_grads(parameters):
+    if isinstance(parameters, torch.Tensor):
+        parameters = [parameters]
+    return [p for p in parameters if p.grad is not None]
+
+
+def _grad_table(ps):
+    """(table, chunk map) of the gradients of `ps` for seg_grad_sumsq / seg_grad_scale (only g and n are read)."""
+    device = ps[0].grad.device
+    for p in ps:
+        g = p.grad
+        if not (g.is_cuda and g.device == device and g.dtype == torch.float32 and not g.is_sparse
+                and g.is_contiguous()):
+            raise NotImplementedError("seg_amd.grad_norm needs contiguous fp32 gradients on one CUDA device")
+    sizes = tuple(p.grad.numel() for p in ps)
+    cm = _CHUNK_MAPS.get((sizes, device))
+    if cm is None:
+        if len(_CHUNK_MAPS) >= 8:
+            _CHUNK_MAPS.clear()
+        cm = _CHUNK_MAPS[(sizes, device)] = _chunk_map(sizes, device)
+    rows = [(0, p.grad.data_ptr(), 0, 0, n, 0.0, 1.0, 1.0, 0.0) for p, n in zip(ps, sizes)]
+    return _pack_w(rows).pin_memory().to(device, non_blocking=True), cm
+
+
+def _norm(ps, max_norm):
+    device = ps[0].grad.device
+    table, cm = _grad_table(ps)
+    out = torch.empty(3, dtype=torch.float32, device=device)
+    if cm.shape[0] == 0:  # only empty gradients
+        out.copy_(torch.tensor([0.0, 1.0, 0.0]))
+        return out, table, cm
+    work = torch.empty(query("seg_grad_norm_workspace_floats", cm.shape[0]), dtype=torch.float32, device=device)
+    call("seg_grad_sumsq", table.data_ptr(), cm.data_ptr(), cm.shape[0], _CHUNK,
+         0.0 if max_norm is None else float(max_norm), work.data_ptr(), out.data_ptr(),
+         torch.cuda.current_stream(device).cuda_stream)
+    return out, table, cm
+
+
+def grad_norm(parameters, max_norm=None) -> torch.Tensor:
+    """[norm, coef, nonfinite] as a 3-element fp32 device tensor, with no host wait: the global L2 norm of the
+    gradients of `parameters` (those with `.grad is None` are skipped), the clip coefficient
+    min(max_norm / (norm + 1e-6), 1) (1 without a max_norm; NaN for a NaN norm, as torch's clamp gives) and 1.0
+    if the norm is inf or NaN.  Run to run the result is bitwise the same (fixed summation order, no atomics).
+    `out[1:2]` is what `step(grad_scale=...)` takes.  No gradients at all: [0, 1, 0].  CUDA gradients only."""
+    params = [parameters] if isinstance(parameters, torch.Tensor) else list(parameters)
+    ps = _with_grads(params)
+    if not ps:
+        return torch.tensor([0.0, 1.0, 0.0], device=params[0].device if params else None)
+    return _norm(ps, max_norm)[0]
+
+
+def clip_grad_norm_(parameters, max_norm, error_if_nonfinite=False) -> torch.Tensor:
+    """torch.nn.utils.clip_grad_norm_ for the L2 norm: scales the gradients in place so that their global norm is
+    at most `max_norm` (> 0) and returns the norm before clipping as a 0-dim device tensor.  grad_norm followed by
+    seg_grad_scale: two reads of the gradients and, only when something is clipped, one write; no host wait unless
+    error_if_nonfinite, which reads the flag and raises RuntimeError as torch does.  CPU gradients (the CPU model
+    composition) and an empty set go to torch's function."""
+    if not float(max_norm) > 0:
+        raise ValueError(f"clip_grad_norm_: max_norm must be positive, got {max_norm}")
+    params = [parameters] if isinstance(parameters, torch.Tensor) else list(parameters)
+    ps = _with_grads(params)
+    if not ps or not ps[0].grad.is_cuda:
+        return torch.nn.utils.clip_grad_norm_(params, max_norm, error_if_nonfinite=error_if_nonfinite)
+    out, table, cm = _norm(ps, max_norm)
+    if error_if_nonfinite and float(out[2]):
+        raise RuntimeError("The total norm of order 2.0 for gradients from `parameters` is non-finite, so it "
+                           "cannot be clipped. To disable this error and scale the gradients by the non-finite "
+                           "norm anyway, set `error_if_nonfinite=False`")
+    call("seg_grad_scale", table.data_ptr(), cm.data_ptr(), cm.shape[0], _CHUNK, out[1:2].data_ptr(),
+         torch.cuda.current_stream(out.device).cuda_stream)
+    return out[0]
+
+
+def decay_groups(model, weight_decay: float):
+    """Two parameter groups for AdamW: the weights of convolutions and linear layers (ndim > 1) with
+    `weight_decay`; every bias and every BatchNorm weight and bias (and anything else) with 0.0.  Each parameter
+    that requires a gradient appears exactly once; what seg_amd.freeze froze is left out."""
+    decay, rest, seen = [], [], set()
+    for mod in getattr(model, "module", model).modules():
+        for name, p in mod.named_parameters(recurse=False):
+            if id(p) in seen or not p.requires_grad:
+                continue
+            seen.add(id(p))
+            is_weight = isinstance(mod, (nn.modules.conv._ConvNd, nn.Linear)) and name == "weight" and p.ndim > 1
+            (decay if is_weight else rest).append(p)
+    return [{"params": decay, "weight_decay": weight_decay}, {"params": rest, "weight_decay": 0.0}]

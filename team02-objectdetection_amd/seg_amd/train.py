@@ -11,6 +11,9 @@ MI355X differences (results are the same):
     seg_amd model, the loss is computed by the fused upsample+cross-entropy
     kernels (`model.forward_loss`), so the 168 MB of full-resolution logits
     per bs=32 batch are never written;
+  * `max_grad_norm` (not in the reference) clips the gradients' global L2 norm before
+    every step; with seg_amd.Adam / seg_amd.AdamW the coefficient stays on the device
+    and is applied inside the step (seg_amd/optim.py);
   * under torch.distributed the gradients are averaged across ranks by
     seg_amd.ddp (RCCL all-reduce overlapped with the backward) and only
     rank 0 prints and writes checkpoints.
@@ -81,24 +84,40 @@ def _check_labels(model, inputs):
     _raise_bad_labels(n or 0)
 
 
-def _step_and_loss(model, inputs, optimizer, loss):
+def _step_and_loss(model, inputs, optimizer, loss, max_grad_norm=None):
     """optimizer.step() and loss.item() (src/train.py:39-41) with the fused loss's label check.  With seg_amd.Adam
-    the step is queued at once and skips itself on the device when the batch (on any rank) had an out-of-range
-    label; the host reads the flag after loss.item(), whose wait covers it, and raises -- no host wait before the
-    step and no extra collective.  Other optimizers: the check runs before the step."""
-    from .optim import Adam
+    or seg_amd.AdamW the step is queued at once and skips itself on the device when the batch (on any rank) had an
+    out-of-range label; the host reads the flag after loss.item(), whose wait covers it, and raises -- no host wait
+    before the step and no extra collective.  Other optimizers: the check runs before the step.
+
+    max_grad_norm: clip the global L2 norm of the gradients of the optimizer's parameters (after
+    finish_gradient_sync they are the averaged ones, the same on every rank: no collective).  The two seg_amd
+    optimizers take the coefficient of seg_amd.grad_norm as the step's grad_scale -- nothing waits and .grad stays
+    unclipped; any other optimizer gets seg_amd.clip_grad_norm_ in place, after the label check."""
+    from .optim import Adam, AdamW, clip_grad_norm_, grad_norm
     from .engine import label_flag
     flag = label_flag(model) if inputs.is_cuda else None
-    if flag is None or not isinstance(optimizer, Adam):
+    ours = isinstance(optimizer, (Adam, AdamW))
+    scale = None
+    if max_grad_norm is not None:
+        params = [p for group in optimizer.param_groups for p in group["params"]]
+        if ours and inputs.is_cuda:
+            scale = {"grad_scale": grad_norm(params, max_grad_norm)[1:2]}
+    if flag is None or not ours:
         _check_labels(model, inputs)
-        optimizer.step()
+        if scale is not None:
+            optimizer.step(**scale)
+        else:
+            if max_grad_norm is not None:
+                clip_grad_norm_(params, max_grad_norm)
+            optimizer.step()
         return loss.item()
     core = getattr(model, "module", model)
     host = core.__dict__.get("_segamd_flag_host")
     if host is None:
         host = core.__dict__["_segamd_flag_host"] = torch.zeros(1, dtype=torch.float32).pin_memory()
     host.copy_(flag, non_blocking=True)  # stream-ordered before the step and the loss copy below
-    optimizer.step(skip_if_nonzero=flag)
+    optimizer.step(skip_if_nonzero=flag, **(scale or {}))
     lv = loss.item()                     # waits for this stream: the flag copy has landed
     if float(host[0]):
         optimizer.undo_step_count()      # the device skipped the step: its counters go back too (ADVICE r5)
@@ -116,8 +135,10 @@ def compute_loss(model, criterion, inputs, targets):
 
 
 def train_one_epoch(model, train_loader, criterion, optimizer, device, epoch: int = 0, epochs: int = 1,
-                    progress: bool = True, augment=None) -> float:
+                    progress: bool = True, augment=None, max_grad_norm: float | None = None) -> float:
     """One pass over `train_loader`; returns the mean batch loss (src/train.py:31-44).
+
+    max_grad_norm: clip the gradients' global L2 norm to it before every step (_step_and_loss); None: no clipping.
 
     augment: optional seg_amd.augment.GpuAugment -- the loader then yields decoded
     uint8 batches (images [N,Hs,Ws,3] RGB, masks [N,Hs,Ws] raw class ids) and the
@@ -145,7 +166,7 @@ def train_one_epoch(model, train_loader, criterion, optimizer, device, epoch: in
             sync()
         # the update never sees an out-of-range label's NaN gradients, on any rank (nn.CrossEntropyLoss raises in
         # the forward): seg_amd.Adam skips its step on the device, everything else is checked before the step
-        lv = _step_and_loss(model, inputs, optimizer, loss)
+        lv = _step_and_loss(model, inputs, optimizer, loss, max_grad_norm)
         train_loss += lv
         nb += 1
         if bar is not None:
@@ -236,7 +257,7 @@ def validate(model, val_loader, criterion, device, progress: bool = True, epoch:
 def train_model(model, train_loader, criterion, optimizer, device, epochs=10,
                 checkpoint_pattern: str | None = "Models/obj/obj_MOB_1_epoch_{epoch}.pth", progress: bool = True,
                 augment=None, val_loader=None, best_checkpoint: str | None = None, freeze=None,
-                freeze_epochs: int | None = None):
+                freeze_epochs: int | None = None, max_grad_norm: float | None = None):
     """Train for `epochs` epochs (src/train.py:6-79).  With `val_loader`, each epoch ends with the
     reference's validation phase (commented out there, src/train.py:46-76): validate(), the
     epoch's result lines, and on an improved validation loss a state_dict at `best_checkpoint`
@@ -244,7 +265,9 @@ def train_model(model, train_loader, criterion, optimizer, device, epochs=10,
 
     freeze: what seg_amd.freeze takes ("backbone", a module, a list of either) -- frozen (parameters and
     BatchNorm statistics) before the first epoch; freeze_epochs=K unfreezes it before epoch K+1, None keeps it
-    frozen for the whole run.  One line is printed at each change; without `freeze` nothing changes."""
+    frozen for the whole run.  One line is printed at each change; without `freeze` nothing changes.
+
+    max_grad_norm: train_one_epoch's -- the gradients' global L2 norm is clipped to it before every step."""
     from .freeze import freeze as _freeze, unfreeze as _unfreeze
     if freeze is not None:
         if isinstance(freeze, (str, nn.Module)):
@@ -265,7 +288,7 @@ def train_model(model, train_loader, criterion, optimizer, device, epochs=10,
         if hasattr(sampler, "set_epoch"):
             sampler.set_epoch(epoch)  # DistributedWeightedSampler: a new shared draw per epoch
         avg_train_loss = train_one_epoch(model, train_loader, criterion, optimizer, device, epoch, epochs, progress,
-                                         augment)
+                                         augment, max_grad_norm)
         val = None
         if val_loader is not None:  # every rank: validate() all-reduces
             val = validate(model, val_loader, criterion, device, progress, epoch, epochs)
