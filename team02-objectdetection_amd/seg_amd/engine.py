@@ -24,6 +24,11 @@ eval: frozen on its running statistics, which it then leaves alone -- and the ba
 with requires_grad needs: grad_frontier() says per op whether it owes parameter gradients and whether anything
 upstream of its input trains.  Both patterns are part of a recorded plan's key (plan_signature).
 
+Backward schedule: one path per decision.  ConvOp.backward is the BatchNorm backward (ConvOp._bn_backward: its four
+forms), the residual hand-off, the data gradient on the main stream and then the parameter gradients, whose placement
+-- behind a side-stream fork now, or deferred to run beside the encoder's memory-bound backward -- Run.param_grads
+alone decides.  A frozen conv runs only its data gradient; an op behind the gradient frontier runs nothing.
+
 Routes: which kernel runs a conv is decided once per program and direction, in one
 place.  pick_routes() gives every ConvOp a Route for its forward, data gradient and
 weight gradient (op.route_f / route_d / route_w): the kernel family, the resolved C
@@ -293,15 +298,20 @@ class ConvOp:
             rt.call(r.name, rt.ptr(i), i.ld, i.N, i.H, i.W, i.C, *self._in_xform(rt),
                     self.wk_f.data_ptr(), rt.ptr(y), y.ld, y.H, y.W, self.stride, s)
         else:
-            if train:  # BN statistics fused into the conv epilogue, one row per tile
-                ntiles, tile_rows = r.tiles
-                stat = rt.tmp(ntiles * 2 * self.cout)
+            if train:  # BN statistics fused into the conv epilogue, one row per tile (r.tiles)
+                stat = rt.tmp(r.tiles[0] * 2 * self.cout)
             self._launch(rt, r, rt.ptr(i), i.ld, i, self.cin_pad, self.wk_f, rt.ptr(y), y, self.cout,
                          self.conv.bias.data_ptr() if self.conv.bias is not None else None, None, 0,
                          stat.data_ptr() if stat is not None else None,
                          self._in_xform(rt) if self.xform is not None else None, self.stride, s)
-        if self.bn is None:
-            return
+        if self.bn is not None:
+            self._bn_forward(rt, train, stat)
+
+    def _bn_forward(self, rt, train, stat):
+        """This op's BatchNorm after its conv: the [4][C] mean / invstd / scale / shift of the batch (train; `stat`:
+        the conv epilogue's tile partials, None after a depthwise conv) or of the running statistics, saved for the
+        backward, then BN + act (+ residual) y -> out unless the consumer applies them on load (lazy)."""
+        s, y = rt.stream, self.y
         bn, C, M = self.bn, self.cout, y.M
         st = torch.empty(4 * C, device=rt.device, dtype=torch.float32)
         mean, invstd, scale, shift = _stat_ptrs(st, C)
@@ -311,14 +321,15 @@ class ConvOp:
             rm = bn.running_mean.data_ptr() if bn.track_running_stats else None
             rv = bn.running_var.data_ptr() if bn.track_running_stats else None
             nbt = bn.num_batches_tracked.data_ptr() if bn.track_running_stats else None
-            if self.kind == "dw" and stat is None:
+            if stat is None:
                 work = rt.tmp(query("seg_chan_workspace_floats", M, C))
                 rt.call(rt.k("seg_bn_stats"), rt.ptr(y), y.ld, M, C, bn.weight.data_ptr(), bn.bias.data_ptr(), bn.eps,
                      bn.momentum, rm, rv, nbt, work.data_ptr(), mean, invstd,
                      scale, shift, s)
             else:
-                # many-tile layers: 16 tiles merged per row before the per-channel finalize (SEG_BN_MERGE=0: direct)
-                nw = query("seg_bn_stats_tiles_work_floats", ntiles, C) if BN_MERGE else 0
+                # many-tile layers (a non-zero workspace size): 16 tiles merged per row before the per-channel finalize
+                ntiles, tile_rows = self.route_f.tiles
+                nw = query("seg_bn_stats_tiles_work_floats", ntiles, C)
                 ws = (rt.tmp(nw).data_ptr(),) if nw else ()
                 rt.call("seg_bn_stats_tiles_ws" if nw else "seg_bn_stats_tiles", stat.data_ptr(), ntiles, tile_rows, M,
                         C, bn.weight.data_ptr(), bn.bias.data_ptr(), bn.eps, bn.momentum, rm, rv, nbt, mean, invstd,
@@ -361,9 +372,6 @@ class ConvOp:
             plan = (ctypes.c_int * 3)()
             query("seg_conv_igemm_plan_b1", M, self.cout, self.cin_pad, self.ks, ctypes.addressof(plan))
             splits, tile, ntl = plan
-            if not PLAN_B1:  # the cost model's tile and split count
-                splits, tile = query("seg_conv_igemm_splits", M, self.cout, self.cin_pad, self.ks), -1
-                ntl = query("seg_conv_igemm_tiles", M, self.cout)
             bufs = rt._mb[("ic", id(self))] = (
                 torch.empty(splits * M * self.cout if splits > 1 else 1, device=rt.device, dtype=torch.float32),
                 torch.zeros(4 * ntl, device=rt.device, dtype=torch.int32), splits, tile)
@@ -407,7 +415,7 @@ class ConvOp:
         return (rt.ptr(py), py.ld, scale, shift, mean, p.act, part.data_ptr()), p
 
     def backward(self, rt):
-        s, y = rt.stream, self.y
+        s = rt.stream
         # grad_frontier: does anything upstream of the input / of the residual want this op's data gradient
         _, dgrad, rgrad = rt.need[rt.cur_op]
         dgrad = dgrad and not self.first
@@ -415,47 +423,7 @@ class ConvOp:
         conv_grads = cw.requires_grad or (cb is not None and cb.requires_grad)
         dA = rt.grad_of(self.out)
         if self.bn is not None:
-            C, M = self.cout, y.M
-            bn = self.bn
-            st = rt.saved[id(self)]
-            mean, invstd, scale, shift = _stat_ptrs(st, C)
-            g_w = rt.grad_param(bn.weight) if bn.weight.requires_grad else None
-            g_b = rt.grad_param(bn.bias) if bn.bias.requires_grad else None
-            # bench.py's "bn_bwd" family: algorithmic bytes of a BatchNorm backward = dA and y read once, dY written
-            # once (3 |Y|), credited to the launch that writes dY
-            abytes = 3 * M * C * rt.es
-            bp = rt.bn_parts.pop(id(self), None)
-            want_dy = dgrad or conv_grads  # else: only the affine gradients (nothing reads dY)
-            dY = Act(rt.tmp_buf(M * r4(C)), 0, r4(C), C, y.N, y.H, y.W) if want_dy else None
-            if not rt.bn_train[id(self)]:
-                # frozen statistics: one pass (seg_bn_frozen_backward), no reduction at all with a frozen affine pair
-                red = g_w is not None or g_b is not None
-                if red or want_dy:
-                    work = rt.tmp(query("seg_chan_workspace_floats", M, C)) if red else None
-                    rt.tcall("bn_bwd", abytes if want_dy else 0, rt.k("seg_bn_frozen_backward"), rt.gptr(dA), dA.ld,
-                             rt.ptr(y), y.ld, M, C, scale, shift, bn.running_mean.data_ptr(),
-                             bn.running_var.data_ptr(), bn.eps, self.act, g_w, g_b,
-                             work.data_ptr() if red else None, rt.ptr(dY) if want_dy else None,
-                             dY.ld if want_dy else 0, s)
-            elif not want_dy:
-                if g_w is not None or g_b is not None:  # the reduction half alone
-                    work = rt.tmp(query("seg_chan_workspace_floats", M, C) + 3 * C)
-                    rt.call(rt.k("seg_bn_bwd_coef"), rt.gptr(dA), dA.ld, rt.ptr(y), y.ld, M, C, bn.weight.data_ptr(),
-                            mean, invstd, scale, shift, self.act, g_w, g_b, work.data_ptr(),
-                            work.data_ptr() + 4 * query("seg_chan_workspace_floats", M, C), s)
-            elif bp is not None and bp[2] == rt.wgen.get(self.out.buf):
-                # the reduction's partials came out of the epilogue of the data gradient that completed dA (nothing
-                # wrote the buffer since): finalize them, then the apply
-                coef = rt.tmp(3 * C)
-                rt.tcall("bn_bwd", 0, "seg_bn_bwd_finalize_tiles", bp[0].data_ptr(), bp[1], M, C,
-                         self.bn.weight.data_ptr(), invstd, g_w, g_b, coef.data_ptr(), s)
-                rt.tcall("bn_bwd", abytes, rt.k("seg_bn_bwd_apply"), rt.gptr(dA), dA.ld, rt.ptr(y), y.ld, M, C, mean,
-                         scale, shift, self.act, coef.data_ptr(), rt.ptr(dY), dY.ld, s)
-            else:
-                work = rt.tmp(query("seg_chan_workspace_floats", M, C) + 3 * C)
-                rt.tcall("bn_bwd", abytes, rt.k("seg_bn_backward"), rt.gptr(dA), dA.ld, rt.ptr(y), y.ld, M, C,
-                         self.bn.weight.data_ptr(), mean, invstd, scale, shift, self.act,
-                         g_w, g_b, work.data_ptr(), rt.ptr(dY), dY.ld, s)
+            dY = self._bn_backward(rt, dA, dgrad or conv_grads)  # None: only the affine gradients (nothing reads dY)
             if self.res is not None and rgrad:
                 rt.add_pending(self.res, dA)
             if dY is None:  # a frozen conv under a trainable BatchNorm affine pair, nothing trainable upstream
@@ -464,7 +432,6 @@ class ConvOp:
         else:
             dY = dA
         dYp = rt.ptr(dY) if dY.buf.startswith("#") else rt.gptr(dY)
-        M = y.M
         if not conv_grads:  # a frozen conv: no side-stream work, only what is upstream of it
             rt.params_done(self.params(), s)
             if dgrad:
@@ -474,41 +441,63 @@ class ConvOp:
         # and nothing on the main stream's data-gradient chain waits for them)
         # gradient tensors handed back to autograd are allocated on the main stream
         # (they outlive the backward; the side stream only writes into them)
-        for p in (self.conv.weight, self.conv.bias):
+        for p in (cw, cb):
             if p is not None and p.requires_grad:
                 rt.grad_param(p)
-        late = FORK_LATE and dgrad
-        if late:  # the data gradient first: the side stream's weight gradient then runs beside
+        if dgrad:  # the data gradient first: the side stream's weight gradient then runs beside
             self._dgrad(rt, dY, dYp, s)  # the next layer's memory-bound BN backward, not this dgrad
-        k = getattr(rt, "cur_op", -1)
-        if WGRAD_TAIL and rt.side is not None and rt.sync is None and 0 <= k < WGRAD_TAIL:
-            # the backward's last layers: their parameter gradients go on the MAIN stream after its last data
-            # gradient (Run.flush_tail), sharing the end-of-step backlog with the side stream
-            for p in (self.conv.weight, self.conv.bias):
-                if p is not None and p.requires_grad:
-                    rt.grad_param(p)
-            rt.tail.append((self, dY, dYp))
-        elif rt.defer is not None and rt.side is not None and k >= rt.defer[0]:
-            # issued later, beside the memory-bound part of the backward (Run.flush_deferred); dY stays valid
-            # (persistent within the run)
-            for p in (self.conv.weight, self.conv.bias):
-                if p is not None and p.requires_grad:
-                    rt.grad_param(p)
-            rt.deferred.append((self, dY, dYp))
+        rt.param_grads(self, dY, dYp)
+
+    def _bn_backward(self, rt, dA, want_dy):
+        """This op's BatchNorm + act backward: the affine gradients the layer owes and, if want_dy, dY (the gradient
+        of the conv's raw output y, in a buffer of its own) from dA; returns dY or None.  Four forms: frozen
+        statistics, the reduction alone, finalize + apply on a data gradient's tile partials (ConvOp._bnout), and
+        the fused reduction + apply."""
+        s, y, bn = rt.stream, self.y, self.bn
+        C, M = self.cout, y.M
+        mean, invstd, scale, shift = _stat_ptrs(rt.saved[id(self)], C)
+        g_w = rt.grad_param(bn.weight) if bn.weight.requires_grad else None
+        g_b = rt.grad_param(bn.bias) if bn.bias.requires_grad else None
+        # bench.py's "bn_bwd" family: algorithmic bytes of a BatchNorm backward = dA and y read once, dY written
+        # once (3 |Y|), credited to the launch that writes dY
+        abytes = 3 * M * C * rt.es
+        bp = rt.bn_parts.pop(id(self), None)
+        dY = Act(rt.tmp_buf(M * r4(C)), 0, r4(C), C, y.N, y.H, y.W) if want_dy else None
+        if not rt.bn_train[id(self)]:
+            # frozen statistics: one pass (seg_bn_frozen_backward), no reduction at all with a frozen affine pair
+            red = g_w is not None or g_b is not None
+            if red or want_dy:
+                work = rt.tmp(query("seg_chan_workspace_floats", M, C)) if red else None
+                rt.tcall("bn_bwd", abytes if want_dy else 0, rt.k("seg_bn_frozen_backward"), rt.gptr(dA), dA.ld,
+                         rt.ptr(y), y.ld, M, C, scale, shift, bn.running_mean.data_ptr(),
+                         bn.running_var.data_ptr(), bn.eps, self.act, g_w, g_b,
+                         work.data_ptr() if red else None, rt.ptr(dY) if want_dy else None,
+                         dY.ld if want_dy else 0, s)
+        elif not want_dy:
+            if g_w is not None or g_b is not None:  # the reduction half alone
+                work = rt.tmp(query("seg_chan_workspace_floats", M, C) + 3 * C)
+                rt.call(rt.k("seg_bn_bwd_coef"), rt.gptr(dA), dA.ld, rt.ptr(y), y.ld, M, C, bn.weight.data_ptr(),
+                        mean, invstd, scale, shift, self.act, g_w, g_b, work.data_ptr(),
+                        work.data_ptr() + 4 * query("seg_chan_workspace_floats", M, C), s)
+        elif bp is not None and bp[2] == rt.wgen.get(self.out.buf):
+            # the reduction's partials came out of the epilogue of the data gradient that completed dA (nothing
+            # wrote the buffer since): finalize them, then the apply
+            coef = rt.tmp(3 * C)
+            rt.tcall("bn_bwd", 0, "seg_bn_bwd_finalize_tiles", bp[0].data_ptr(), bp[1], M, C,
+                     bn.weight.data_ptr(), invstd, g_w, g_b, coef.data_ptr(), s)
+            rt.tcall("bn_bwd", abytes, rt.k("seg_bn_bwd_apply"), rt.gptr(dA), dA.ld, rt.ptr(y), y.ld, M, C, mean,
+                     scale, shift, self.act, coef.data_ptr(), rt.ptr(dY), dY.ld, s)
         else:
-            ctx, sw = rt.fork()
-            with ctx:
-                self._param_grads(rt, dY, dYp, sw)
-        if dgrad and not late:
-            self._dgrad(rt, dY, dYp, s)
+            work = rt.tmp(query("seg_chan_workspace_floats", M, C) + 3 * C)
+            rt.tcall("bn_bwd", abytes, rt.k("seg_bn_backward"), rt.gptr(dA), dA.ld, rt.ptr(y), y.ld, M, C,
+                     bn.weight.data_ptr(), mean, invstd, scale, shift, self.act,
+                     g_w, g_b, work.data_ptr(), rt.ptr(dY), dY.ld, s)
+        return dY
 
     def _param_grads(self, rt, dY, dYp, s):
         """Bias gradient (column sum of dY), weight gradient (split-K slabs + fixed-order
         reduce) and the DDP readiness hook, all on stream `s`."""
         y, M = self.y, self.y.M
-        if DIAG_SKIP_WGRAD is not None and DIAG_SKIP_WGRAD[0] <= getattr(rt, "cur_op", -1) < DIAG_SKIP_WGRAD[1]:
-            rt.params_done(self.params(), s)  # diagnostics only: no conv weight / bias gradients (wrong training)
-            return
         if self.conv.bias is not None and self.conv.bias.requires_grad:
             if self.bn is not None and ZERO_BN_BIAS and rt.bn_train[id(self)]:
                 # conv -> train-mode BatchNorm (src/unet.py:58-59,61-62): the bias shifts its whole channel by
@@ -629,6 +618,12 @@ class Program:
         self.out_hw = (H, W)
         self._n = 0
         self.image = self.new(3, H, W, name=IMAGE)  # NHWC4 copy of the input batch
+        # memoised once the op list is complete (first walk)
+        self._mb_groups = None   # mbconv_groups()
+        self._bn_owner = None    # bn_owner()
+        self._pack_key = None    # what the routes / packed weights / job table were built for (pack)
+        self._fold_key = None    # ... and the folded inference weights (fold)
+        self._fork_events = []   # events of an immediate backward's side-stream forks, reused step after step
 
     def wgrad_defer(self):
         """(from, at): the parameter gradients of ops >= from wait until the backward reaches op `at`, or None.
@@ -646,9 +641,8 @@ class Program:
         """Folded forward: op index -> the (expand, depthwise, project) or (depthwise, project) ConvOps of a
         torchvision InvertedResidual that seg_mbconv_f16 runs as one launch (each intermediate activation
         consumed only inside the block: the lazy BN chain Program.make_lazy built)."""
-        m = getattr(self, "_mb_groups", None)
-        if m is not None:
-            return m
+        if self._mb_groups is not None:
+            return self._mb_groups
         m, ops = {}, self.ops
         ok1 = (lambda op: isinstance(op, ConvOp) and op.kind == "igemm" and op.ks == 1 and op.stride == 1
                and op.bn is not None and op.conv.bias is None and op.cin_pad == op.cin)
@@ -706,10 +700,10 @@ class Program:
     def bn_owner(self):
         """Activation key -> the ConvOp with a BatchNorm whose output it is (the BN-backward reduction target of a
         data gradient writing exactly that region; ConvOp._bnout)."""
-        m = getattr(self, "_bn_owner", None)
-        if m is None:
-            m = self._bn_owner = {op.out.key(): op for op in self.ops if isinstance(op, ConvOp) and op.bn is not None}
-        return m
+        if self._bn_owner is None:
+            self._bn_owner = {op.out.key(): op for op in self.ops if isinstance(op, ConvOp) and op.bn is not None}
+        return self._bn_owner
+
     def new(self, C, H, W, name=None):
         name = name or f"t{self._n}"
         self._n += 1
@@ -736,7 +730,7 @@ class Program:
         consumers re-read every input element once per tap: measured slower, round 3.)"""
         op = self.ops[-1] if self.ops else None
         kinds = ("igemm", "dw") if pointwise else ("igemm",)
-        if pointwise and not (LAZY_PW and a.C % 8 == 0 and a.C >= 16):
+        if pointwise and not (a.C % 8 == 0 and a.C >= 16):
             return None
         if not (isinstance(op, ConvOp) and op.kind in kinds and op.bn is not None and op.res is None
                 and op.out is a and op.y is not a and a.off == 0 and a.ld == r4(a.C)
@@ -752,7 +746,7 @@ class Program:
         rebuilt only when a weight's storage moves (e.g. model.to()) or a tile is forced."""
         convs = [op for op in self.ops if isinstance(op, ConvOp)]
         key = (_TILE_GEN, *(op.conv.weight.data_ptr() for op in convs))
-        if getattr(self, "_pack_key", None) != key:
+        if self._pack_key != key:
             self._build_pack(convs, key)
         if self._njobs:
             rt.call("seg_pack_batch", self._jobs.data_ptr(), self._njobs, self._pack_blocks, rt.stream)
@@ -788,7 +782,7 @@ class Program:
         statistics change (Predictor.refresh)."""
         convs = [op for op in self.ops if isinstance(op, ConvOp)]
         key = tuple(op.conv.weight.data_ptr() for op in convs)
-        if getattr(self, "_fold_key", None) != key:
+        if self._fold_key != key:
             self._build_fold(convs, key)
         call("seg_bn_fold_batch", self._fjobs.data_ptr(), len(convs), self._fmax, stream)
         if self._fpjobs is not None:
@@ -986,9 +980,6 @@ def _pick_wgrad(math, op):
     if dense3 and not bf and WINOGRAD and WINOGRAD_WGRAD and op.xform is None:
         # seg_conv_wino_wgrad_pick: 2 = the all-points kernel (seg_conv_wino_wgrad16), 1 = the per-point one
         p = query("seg_conv_wino_wgrad_pick", y.N, y.H, y.W, K, cout)
-        if p == 2 and not WINO_WGRAD16:  # A/B switch: the round-5 rule (per-point kernel, deep convs)
-            T = y.N * (y.H // 2) * (y.W // 2)
-            p = int(K >= 128 and cout >= 128 and (T >= 65536 or min(K, cout) >= 256))
         if p:
             name = "seg_conv_wino_wgrad16" if p == 2 else "seg_conv_wino_wgrad"
             splits = query(name + "_splits", y.N, y.H, y.W, K, cout)
@@ -1194,14 +1185,21 @@ class Run:
         self.written = {}     # grad buffer name -> list of (lo, hi) channel ranges
         self.pending = {}     # Act.key() -> addend Act (residual upstream gradient)
         self.grads = {}       # id(param) -> grad tensor
-        self.flat = None      # recorded run: one flat fp32 buffer holding every parameter gradient
+        self.flat = None      # recorded run: one flat fp32 buffer holding every parameter gradient (Plan.forward)
+        self.flat_slots = {}  # ... id(param) -> (offset, elements) in it
         self.sync = None
         self._tmp_n = 0
         self.side = side      # side stream of the parameter gradients (recorded backward)
+        self.main = None      # immediate backward with overlap (backward_from_logits): torch's current stream,
+        self._side_ctx = None  # and the side stream's context that every fork re-enters
         self._n_fork = 0      # side-stream forks so far (index into the program's event pool)
-        self.deferred = []    # (op, dY, dY ptr) whose parameter gradients wait for flush_deferred (WGRAD_DEFER)
-        self.tail = []        # ... for flush_tail (WGRAD_TAIL)
+        self.cur_op = -1      # index of the op whose backward is running
+        self.deferred = []    # (op, dY, dY ptr) whose parameter gradients wait for flush_deferred
         self.defer = prog.wgrad_defer()  # (from, at) of the deferred parameter gradients, or None
+        # the fused loss's forward (_loss_forward), read by its backward
+        self.target = self.weight = self.stats = None  # labels, class weights, the [loss, count, ...] buffer
+        self.label_smoothing = 0.0
+        self.plain_loss = True  # no class weights, smoothing or "sum": the seg_ce_* kernels (else seg_cew_*)
 
     def k(self, name: str) -> str:
         """C-ABI entry point of an activation kernel for this run's storage type."""
@@ -1297,7 +1295,7 @@ class Run:
             self.rec.wait(self.side.cuda_stream, ev)
             return contextlib.nullcontext(), self.side.cuda_stream
         # events are reused step after step (a wait binds to the record before it)
-        pool = self.prog.__dict__.setdefault("_fork_events", [])
+        pool = self.prog._fork_events
         if self._n_fork == len(pool):
             pool.append(torch.cuda.Event())
         ev = pool[self._n_fork]
@@ -1305,6 +1303,17 @@ class Run:
         ev.record(self.main)
         self.side.wait_event(ev)
         return self._side_ctx, self.side.cuda_stream
+
+    def param_grads(self, op, dY, dYp):
+        """Where the parameter gradients of the running op go: beside the main stream now (behind a fork), or, for
+        the ops of the deferred range (Program.wgrad_defer), later, beside the memory-bound part of the backward
+        (flush_deferred; dY stays valid, it is persistent within the run)."""
+        if self.defer is not None and self.side is not None and self.cur_op >= self.defer[0]:
+            self.deferred.append((op, dY, dYp))
+            return
+        ctx, sw = self.fork()
+        with ctx:
+            op._param_grads(self, dY, dYp, sw)
 
     def flush_deferred(self):
         """Issue the deferred parameter gradients on the side stream, in backward order, behind one fork."""
@@ -1315,12 +1324,6 @@ class Run:
             for op, dY, dYp in self.deferred:
                 op._param_grads(self, dY, dYp, sw)
         self.deferred = []
-
-    def flush_tail(self):
-        """The WGRAD_TAIL parameter gradients on the main stream, after every data gradient of the backward."""
-        for op, dY, dYp in self.tail:
-            op._param_grads(self, dY, dYp, self.stream)
-        self.tail = []
 
     def join(self):
         if self.side is None:
@@ -1495,23 +1498,23 @@ class Run:
                     self.rec.label = f"{k}:bwd"
                 self.prog.ops[k].backward(self)
             self.flush_deferred()
-            self.flush_tail()
         finally:
             self.join()
         if DEBUG_KEEP_RUN:
             LAST_RUN = self
 
 
-# Engine switches.  Environment switches (SEG_*) are the A/B knobs of measured design choices, read at import;
-# the module constants below them are diagnostics the tests flip directly (monkeypatch), not user settings.
+# Engine switches: the ones a test, bench.py, the Predictor or INTEGRATION.md uses.  Environment switches (SEG_*) are
+# the A/B knobs of measured design choices, read at import; the module constants below them are diagnostics the tests
+# flip directly (monkeypatch), not user settings.  (The switches of finished experiments are gone with the paths only
+# they selected; DESIGN.md keeps their measurements.)
 #
 # Parameter gradients (weight / bias / BN-affine readiness) run on a second HIP stream
 # beside the data-gradient chain: the compute-bound 3x3 weight gradients overlap the
 # memory-bound BatchNorm / depthwise / 1x1 kernels of the main stream.  Results are the
-# same either way (the kernels and their reduction orders do not change).
+# same either way (the kernels and their reduction orders do not change).  A layer's fork comes after its data
+# gradient (ConvOp.backward; measured against forking first: f32 +1.5 %, bf16io +-0).
 OVERLAP = os.environ.get("SEG_OVERLAP", "1") == "1"
-# fork the weight-gradient side stream after the layer's data gradient (measured: f32 +1.5 %, bf16io +-0)
-FORK_LATE = os.environ.get("SEG_FORK_LATE", "1") == "1"
 # Winograd F(2x2,3x3) for the deep f32 3x3 convs (read when a program's weights are first
 # packed); SEG_WINO=0 routes them to the LDS-halo / implicit-GEMM kernels instead.
 WINOGRAD = os.environ.get("SEG_WINO", "1") == "1"
@@ -1525,9 +1528,6 @@ WGRAD2 = os.environ.get("SEG_WGRAD2", "1") == "1"
 # BN backward is latency-bound
 BNOUT = os.environ.get("SEG_BNOUT", "1") == "1"
 BNOUT_MAX_TILES = int(os.environ.get("SEG_BNOUT_MAX_TILES", "1024"))
-# lazy BatchNorm for 1x1 consumers (the inverted residuals' project convs, OutConv's last
-# conv): SEG_LAZY_PW=0 keeps the separate BN-apply pass (read at program build)
-LAZY_PW = os.environ.get("SEG_LAZY_PW", "1") == "1"
 # the bias gradient of a conv followed by train-mode BatchNorm is exactly zero: write zeros instead of
 # reducing dY (SEG_ZERO_BN_BIAS=0 keeps the reduction, whose result is rounding noise)
 ZERO_BN_BIAS = os.environ.get("SEG_ZERO_BN_BIAS", "1") == "1"
@@ -1553,32 +1553,19 @@ WGRAD_DEFER = tuple(int(v) for v in _wd.split(":")) if _wd else None
 # bf16io: the decoder's parameter gradients deferred until the backward reaches the encoder (Program.wgrad_defer);
 # SEG_DEFER_DECODER=0 = off
 DEFER_DECODER = os.environ.get("SEG_DEFER_DECODER", "1") == "1"
-# SEG_WGRAD_TAIL=K (A/B): the parameter gradients of program ops < K go on the main stream after the backward's last
-# data gradient instead of on the side stream
-WGRAD_TAIL = int(os.environ.get("SEG_WGRAD_TAIL", "0"))
-# many-tile BN statistics merged 16 tiles per row before the per-channel finalize; SEG_BN_MERGE=0 = direct
-BN_MERGE = os.environ.get("SEG_BN_MERGE", "1") == "1"
 
-# Diagnostics only (wrong training): SEG_DIAG_SKIP_WGRAD=1 issues no conv weight / bias gradient at all -- the step
-# time of the main stream's work alone, with no side-stream contention (the weight gradients' share of the step,
-# DESIGN round 6); SEG_DIAG_SKIP_WGRAD=lo:hi skips only those of the program ops lo <= k < hi
-_dsw = os.environ.get("SEG_DIAG_SKIP_WGRAD", "0")
-DIAG_SKIP_WGRAD = None if _dsw == "0" else (0, 1 << 30) if _dsw == "1" else tuple(int(v) for v in _dsw.split(":"))
 # Diagnostics (tests flip these): the Winograd transforms one at a time (parity attribution,
 # tests/test_gpu_unet_cfg5.py) ...
-WINOGRAD_WGRAD = True  # the F(3x3,2x2) weight gradients
-# ... on the all-points kernel (seg_conv_wino_wgrad16; SEG_WINO_WGRAD16=0: the round-5 choice, A/B only)
-WINO_WGRAD16 = os.environ.get("SEG_WINO_WGRAD16", "1") != "0"
+WINOGRAD_WGRAD = True  # the F(3x3,2x2) weight gradients (seg_conv_wino_wgrad_pick: all-points or per-point kernel)
 WINOGRAD_FWD = True    # the F(2x2,3x3) forward
 WINOGRAD_DGRAD = True  # ... and data-gradient transforms
 # ... and the fp16 inference (Predictor, BASELINE configs[3]) fusions against their unfused launches: each inverted
 # residual of the folded forward as one launch (seg_mbconv_f16), the stem forming the preprocessed frame on load
-# (seg_stem_pre_f16), outconv's 1x1 -> BN -> ReLU -> 1x1 head in one launch (seg_pw2_f16), and the folded convs on
-# seg_conv_igemm_plan_b1's tile / split count (the batch-1 decoder convs) instead of the training cost model's
+# (seg_stem_pre_f16), outconv's 1x1 -> BN -> ReLU -> 1x1 head in one launch (seg_pw2_f16).  (The other folded convs
+# always run on seg_conv_igemm_plan_b1's tile / split count, the batch-1 decoder convs' plan.)
 MBCONV = True
 STEM_PRE = True
 PW2 = True
-PLAN_B1 = True
 _SIDE = {}
 
 
@@ -1714,7 +1701,7 @@ def _loss_forward(run, t, ignore_index, confusion=None, weight=None, label_smoot
     else:
         run.call(run.k("seg_ce_upsample_eval"), run.ptr(lo), lo.ld, N, lo.H, lo.W, lo.C, t.data_ptr(), Ho, Wo,
                  ignore_index, work.data_ptr(), stats.data_ptr(), confusion.data_ptr(), s)
-    run.target, run.stats = t, stats
+    run.stats = stats
     return stats
 
 
@@ -1807,7 +1794,7 @@ class Plan:
             run.sync = self.sync
             if self.needs_grad:
                 ps = [p for p in self.prog.params() if p.requires_grad]
-                run.flat_slots, off = {}, 0
+                off = 0
                 for p in ps:
                     run.flat_slots[id(p)] = (off, p.numel())
                     off += p.numel()
