@@ -35,9 +35,10 @@ extern "C" {
  * head (src/unet.py:113,116) and torchvision's expand/project 1x1 convs
  * (reached through src/unet.py:15-19); with mode-1 packed weights it is also the
  * data gradient of those (stride-1) convs.  ks in {1,3}.  `stat` (optional):
- * per-row-tile BatchNorm partials of `out` ([row_tiles][2][Cout]: tile sum, tile
- * M2), consumed by seg_bn_stats_tiles -- the BN statistics pass fused into the
- * conv epilogue. */
+ * per-row-tile BatchNorm partials of conv + bias ([row_tiles][2][Cout]: tile sum, tile
+ * M2 about the tile mean; from the fp32 accumulators, before `add` and before any
+ * rounding to the storage type), consumed by seg_bn_stats_tiles -- the BN statistics
+ * pass fused into the conv epilogue. */
 int seg_conv_igemm(const float* in, long ldin, int N, int H, int W, int Cin,
                    const float* wk, int ldk, const float* bias,
                    float* out, long ldout, int Ho, int Wo, int Cout,
@@ -129,10 +130,21 @@ int seg_conv_igemm_bnout(const float* in, long ldin, int N, int H, int W, int Ci
                          const float* by, long ldby, const float* bscale, const float* bshift,
                          const float* bmean, int bact, float* bpart, hipStream_t stream);
 
-/* Row tiles (and their height) seg_conv_igemm uses for an M x Cout output. */
-/* Tuning hook: force tile configuration t (0..7) for the following
- * seg_conv_igemm calls of this process, -1 = the built-in cost model. */
+/* The implicit GEMM's tile table: BM x BN output rows x channels per block, waves per block.
+ *    0  128x128  4     1   64x128  4     2  128x64   4     3   64x64   4     4  128x96   4
+ *    5  128x160  4     6  256x32   4     7  128x32   4     8  128x128  8     9  128x128  8
+ *   10  256x128  8    11  128x256  8    12  128x64   8    13  256x64   8    14   64x128  8
+ * (8 and 9 differ in the wave layout: 64x32 and 32x64 accumulators per wave.)  The cost model picks among
+ * 0..7; 8..14 are reached through the hook below and the `tile` argument of the _ic entry points.
+ * seg_conv_igemm_bnout* needs 64 % (BN / v) == 0, v = 4 (fp32 storage) or 8 (bf16) output elements per
+ * 16-byte store: every tile but 4 and 5 (seg_conv_igemm_bnout_ok).
+ * Tuning hook: force tile configuration t (0..14) for the following seg_conv_igemm* launches and
+ * seg_conv_igemm_row_tiles / _tiles / _tile / _bnout_ok queries of this process, -1 = the built-in cost
+ * model.  Tile choice does not change results, except the row partition of the BN partials. */
 int seg_igemm_force_tile(int t);
+/* The table entry an M x Cout output runs on. */
+int seg_conv_igemm_tile(long M, int Cout);
+/* Row tiles (and their height) seg_conv_igemm uses for an M x Cout output. */
 int seg_conv_igemm_row_tiles(long M, int Cout, int* tile_rows);
 
 /* Pack w[Cout][Cin][ks][ks]: mode 0 -> wk[Cout][ldk] (forward; tap runs padded

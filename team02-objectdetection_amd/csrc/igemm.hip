@@ -135,20 +135,24 @@ SEG_API int seg_conv_igemm_splits(long M, int Cout, int Cin, int ks) {
   return igemm_splits(M, Cout, ks * ks * Cin);
 }
 
-// Tuning hook: force tile configuration t (0..7, see kTiles) for every following
-// seg_conv_igemm / seg_conv_igemm_row_tiles call of this process; -1 restores the
-// cost model.  Tile choice never changes results (each output is the same
-// k-ordered fmaf chain) except the BN-statistics tile partition.
+// Tuning hook: force tile configuration t (0..14, see kTiles and the table in include/segamd.h)
+// for every following seg_conv_igemm* / seg_conv_igemm_row_tiles / _tiles / _bnout_ok call of
+// this process; -1 restores the cost model.  Tile choice never changes results (each output is
+// the same k-ordered fmaf chain) except the BN-statistics tile partition
+// (tests/test_gpu_igemm_tiles.py holds every tile to that, bitwise).
 SEG_API int seg_igemm_force_tile(int t) {
-  if (t < -1 || t >= (int)(sizeof(kTiles) / sizeof(kTiles[0]))) return (int)hipErrorInvalidValue;
+  if (t < -1 || t >= kNumTiles) return (int)hipErrorInvalidValue;
   seg_igemm_forced_tile = t;
   return 0;
 }
 
+// The tile table entry an M x Cout output runs on (the forced tile, else the cost model's).
+SEG_API int seg_conv_igemm_tile(long M, int Cout) { return pick_tile(M, Cout); }
+
 // Row tiling seg_conv_igemm uses for an M x Cout output: returns the number of
 // row tiles (= rows of its optional BN-statistics partials) and their height.
 SEG_API int seg_conv_igemm_row_tiles(long M, int Cout, int* tile_rows) {
-  const int bm = kTileBM[pick_tile(M, Cout)];
+  const int bm = kTiles[pick_tile(M, Cout)].bm;
   if (tile_rows) *tile_rows = bm;
   return (int)((M + bm - 1) / bm);
 }

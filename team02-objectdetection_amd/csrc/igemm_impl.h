@@ -807,7 +807,7 @@ constexpr TileCfg kTiles[] = {
     {128, 64, 32, 32, 0.0f}, {256, 64, 64, 32, 0.0f}, {64, 128, 32, 32, 0.0f},
 };
 
-constexpr int kTileBM[] = {128, 64, 128, 64, 128, 128, 256, 128, 128, 128, 256, 128, 128, 256, 64};
+constexpr int kNumTiles = (int)(sizeof(kTiles) / sizeof(kTiles[0]));  // the table documented in include/segamd.h
 
 int pick_tile(long M, int N);
 // seg_conv_igemm_bnout*: the picked tile's epilogue holds one column vector per lane (64 % (BN / VO) == 0)

@@ -28,6 +28,7 @@ PROTOTYPES = {
                                 _V, _I, _V]),
     "seg_conv_igemm_splits": (_I, [_L, _I, _I, _I]),
     "seg_igemm_force_tile": (_I, [_I]),
+    "seg_conv_igemm_tile": (_I, [_L, _I]),
     "seg_conv_halo_ok": (_I, [_I, _I, _I, _I, _I]),
     "seg_conv_halo_pick": (_I, [_I, _I, _I, _I, _I]),
     "seg_conv_halo_row_tiles": (_I, [_I, _I, _I]),

@@ -155,11 +155,11 @@ def test_forced_tile_repicks_routes():
         assert all(a is b for a, b in zip(first, (op.route_f for op in prog.ops if isinstance(op, engine.ConvOp))))
         assert rt.calls == ["seg_pack_batch"] * 2
         forced = []
-        for tile in range(8):  # seg_igemm_force_tile: configurations 0..7
+        for tile in range(15):  # seg_igemm_force_tile: configurations 0..14
             engine.force_tiles(igemm=tile)
             prog.pack(rt)
             forced.append(gen.table(prog))
-        # the tile heights differ, so no single geometry can hold for all eight forced tiles
+        # the tile heights differ, so no single geometry can hold for all the forced tiles
         assert any(t != table0 for t in forced)
         assert any(a is not b for a, b in zip(first, (op.route_f for op in prog.ops if isinstance(op, engine.ConvOp))))
         engine.force_tiles(igemm=-1)
