@@ -439,6 +439,44 @@ int seg_cew_upsample_eval(const float* low, long ld, int N, int H, int W, int C,
                           const long long* labels, int Ho, int Wo, int ignore_index,
                           const float* class_weight, float label_smoothing, int reduction,
                           float* work, float* out4, long long* confusion, hipStream_t stream);
+/* seg_amd.SegLoss: a focal term and a soft Dice term beside cross-entropy, fused with the same
+ * upsample (same grid, same pixel -> thread mapping, the full-resolution logits never stored).
+ * Over the valid pixels V, with s_p = softmax(z_p), pt_p = s_p[y_p] and w = class_weight (ones
+ * when NULL):
+ *   F    = sum_p w[y_p] (1 - pt_p)^gamma (-log pt_p) / D,   D = sum_p w[y_p]      (gamma > 0)
+ *   F    = seg_cew_*'s mean loss with label_smoothing                             (gamma == 0)
+ *   I_c = sum_p s_p[c] [y_p = c],  S_c = sum_p s_p[c],  T_c = sum_p [y_p = c],  U_c = S_c + T_c + dice_smooth
+ *   Dice = sum_c m_c (1 - (2 I_c + dice_smooth) / U_c) / max(M, 1),  m_c = [T_c > 0],  M = sum_c m_c
+ *   loss = ce F + dice Dice   (a term whose coefficient is 0 is left out)
+ *   dloss/dz_p[k] = g / D ce [(1 - eps) w[y] f_p (s_k - [k = y]) + (eps / C) (s_k sum_c w[c] - w[k])]
+ *                   + g dice s_k (q_k - sum_c q_c s_c),
+ *   f_p = (1 - pt)^gamma - gamma pt (1 - pt)^(gamma - 1) log pt,  q_c = b_c - a_c [c = y],
+ *   a_c = m_c 2 / (M U_c),  b_c = m_c (2 I_c + dice_smooth) / (M U_c^2).
+ * out6 = [loss, D, #labels outside [0, C) that are not ignore_index, #valid pixels, F, Dice]: the
+ * first four slots are out4's.  table: 64 floats in device memory, a_c at [c] and b_c at [32 + c],
+ * written by _loss / _eval and read by _grad, whose `stats` is their out6.  No float atomics: two
+ * calls on the same inputs agree bitwise.  _eval adds the confusion matrix of seg_ce_upsample_eval.
+ * An out-of-range label makes the loss and every gradient NaN.  `work` >=
+ * seg_sl_workspace_floats(N*Ho*Wo).  hipErrorInvalidValue before any launch: a negative or
+ * non-finite ce, dice or focal_gamma, ce and dice both 0, dice_smooth <= 0, label_smoothing outside
+ * [0, 1] or > 0 with focal_gamma > 0, C outside [1, 32], ld (ldh) % 4 != 0 or < C, or (_eval)
+ * confusion NULL. */
+long seg_sl_workspace_floats(long pixels);
+int seg_sl_upsample_loss(const float* low, long ld, int N, int H, int W, int C,
+                         const long long* labels, int Ho, int Wo, int ignore_index,
+                         const float* class_weight, float label_smoothing, float ce, float dice,
+                         float focal_gamma, float dice_smooth, float* work, float* out6, float* table,
+                         hipStream_t stream);
+int seg_sl_upsample_eval(const float* low, long ld, int N, int H, int W, int C,
+                         const long long* labels, int Ho, int Wo, int ignore_index,
+                         const float* class_weight, float label_smoothing, float ce, float dice,
+                         float focal_gamma, float dice_smooth, float* work, float* out6, float* table,
+                         long long* confusion, hipStream_t stream);
+int seg_sl_upsample_grad(const float* low, long ld, int N, int H, int W, int C,
+                         const long long* labels, int Ho, int Wo, int ignore_index,
+                         const float* class_weight, float label_smoothing, float ce, float dice,
+                         float focal_gamma, const float* grad_out, const float* stats,
+                         const float* table, float* dhigh, long ldh, hipStream_t stream);
 
 /* ---- inference (inference.py: preprocess_image :28-46, model.eval() forward
  *      :23-25,162-163, overlay_predictions' argmax + resize :64-70) ---------- */
@@ -552,6 +590,16 @@ int seg_cew_upsample_eval_bf16io(const seg_bf16* low, long ld, int N, int H, int
 int seg_cew_upsample_grad_bf16io(const seg_bf16* low, long ld, int N, int H, int W, int C, const long long* labels, int
     Ho, int Wo, int ignore_index, const float* class_weight, float label_smoothing, const float* grad_out, const float*
     stats, seg_bf16* dhigh, long ldh, hipStream_t stream);
+int seg_sl_upsample_loss_bf16io(const seg_bf16* low, long ld, int N, int H, int W, int C, const long long* labels, int
+    Ho, int Wo, int ignore_index, const float* class_weight, float label_smoothing, float ce, float dice, float
+    focal_gamma, float dice_smooth, float* work, float* out6, float* table, hipStream_t stream);
+int seg_sl_upsample_eval_bf16io(const seg_bf16* low, long ld, int N, int H, int W, int C, const long long* labels, int
+    Ho, int Wo, int ignore_index, const float* class_weight, float label_smoothing, float ce, float dice, float
+    focal_gamma, float dice_smooth, float* work, float* out6, float* table, long long* confusion, hipStream_t stream);
+int seg_sl_upsample_grad_bf16io(const seg_bf16* low, long ld, int N, int H, int W, int C, const long long* labels, int
+    Ho, int Wo, int ignore_index, const float* class_weight, float label_smoothing, float ce, float dice, float
+    focal_gamma, const float* grad_out, const float* stats, const float* table, seg_bf16* dhigh, long ldh, hipStream_t
+    stream);
 int seg_upsample_fwd_bf16io(const seg_bf16* in, long ldin, int N, int H, int W, int C, seg_bf16* out, long ldout, int
     Ho, int Wo, int ac, hipStream_t stream);
 int seg_upsample_bwd_bf16io(const void* dout, long ldout, int nchw_grad, int N, int Ho, int Wo, int C, seg_bf16* din,

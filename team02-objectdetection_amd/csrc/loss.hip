@@ -473,3 +473,381 @@ SEG_API int seg_cew_upsample_grad_bf16io(const __bf16* low, long ld, int N, int 
   return ce_grad_impl(low, ld, N, H, W, C, labels, Ho, Wo, ignore_index, grad_out, stats, dhigh, ldh, stream,
                       CeOpt{class_weight, label_smoothing, 0});
 }
+
+// ---- focal term and soft Dice beside cross-entropy: seg_sl_* (the criterion is seg_amd.SegLoss) ----
+// Over the valid pixels V, with s_p = softmax(z_p), pt_p = s_p[y_p], w the class weights (all ones when NULL):
+//   F    = sum_p w[y_p] (1 - pt_p)^gamma (-log pt_p) / D,  D = sum_p w[y_p]   (gamma > 0; label smoothing is then 0)
+//   F    = the seg_cew_* mean loss ((1 - eps) nll + (eps / C) smooth) / D     (gamma == 0)
+//   I_c  = sum_p s_p[c] [y_p = c],  S_c = sum_p s_p[c],  T_c = sum_p [y_p = c],  U_c = S_c + T_c + smooth,
+//   Dice = sum_c m_c (1 - (2 I_c + smooth) / U_c) / max(M, 1),  m_c = [T_c > 0],  M = sum_c m_c,
+//   loss = ce F + dice Dice    (a term whose coefficient is 0 is left out, so its 0/0 never reaches the loss).
+// One pass over the pixels writes, per block, the five partials of the seg_cew_* kernels, the focal sum and I_c, S_c,
+// T_c: register accumulators, the wave butterfly, the four waves through LDS in a fixed order -- no float atomics,
+// so two calls agree bitwise (T_c is an LDS integer count: exact).  The partials lie column-major, part[col * nblk +
+// block], so that the one-block fp64 finalize reads them coalesced; it writes stats = [loss, D, #out-of-range
+// labels, #valid, F, Dice] and the table of the Dice gradient's per-class coefficients
+//   a_c = m_c 2 / (M U_c)  at table[c],   b_c = m_c (2 I_c + smooth) / (M U_c^2)  at table[32 + c]
+// (d Dice / d s_p[c] = q_c = b_c - a_c [c = y_p]).  The gradient kernel reads them as wave-uniform values, like the
+// class weights:
+//   dz_k = (g / D) ce [(1 - eps) w[y] f_p (s_k - [k = y]) + (eps / C) (s_k sum_c w[c] - w[k])]
+//          + g dice s_k (q_k - sum_c q_c s_c),     f_p = (1 - pt)^gamma - gamma pt (1 - pt)^(gamma - 1) log pt.
+// Numerical form: 1 - pt is sum_{c != y} e_c / sum_c e_c, never 1.f - pt (no correct bit is left of that when the
+// label's class dominates), and s_y - 1 is its negative; f_p is written (1 - pt)^gamma (1 + gamma pt (-log pt) /
+// (1 - pt)) -- two non-negative terms, no power with a negative exponent -- and f_p and the focal loss term are
+// exactly 0 where 1 - pt is 0.
+namespace {
+
+constexpr int SL_FIXED = 6;                       // nll, sum of w[y], #out-of-range, smooth, #valid, focal
+constexpr int SL_COLS = SL_FIXED + 3 * CMAX;      // + I_c, S_c, T_c
+
+struct SlOpt {
+  const float* cw;  // C class weights in device memory, or NULL = all ones
+  float eps;        // label smoothing (gamma == 0 only)
+  float ce, dice;   // the two coefficients
+  float gamma;      // focal exponent
+  float smooth;     // dice_smooth
+};
+
+inline bool sl_opt_ok(const SlOpt& o) {
+  return std::isfinite(o.eps) && std::isfinite(o.ce) && std::isfinite(o.dice) && std::isfinite(o.gamma) &&
+         std::isfinite(o.smooth) && o.eps >= 0.f && o.eps <= 1.f && o.ce >= 0.f && o.dice >= 0.f &&
+         (o.ce > 0.f || o.dice > 0.f) && o.gamma >= 0.f && o.smooth > 0.f && !(o.eps > 0.f && o.gamma > 0.f);
+}
+
+template <int CP, typename T, bool EVAL>
+__global__ __launch_bounds__(256) void sl_up_loss_kernel(const T* __restrict__ low, long ld, int N, int H, int W,
+                                                         int C, const long long* __restrict__ labels, int Ho, int Wo,
+                                                         float sh, float sw, int ignore_index,
+                                                         float* __restrict__ part,
+                                                         unsigned long long* __restrict__ confusion, SlOpt o) {
+  constexpr int NR = SL_FIXED + 2 * CP;
+  __shared__ float red[4][NR];
+  __shared__ int tcnt[CP];
+  __shared__ int hist[EVAL ? CMAX * CMAX : 1];
+  if (threadIdx.x < CP) tcnt[threadIdx.x] = 0;
+  if constexpr (EVAL)
+    for (int i = threadIdx.x; i < C * C; i += blockDim.x) hist[i] = 0;
+  __syncthreads();
+  const long total = (long)N * Ho * Wo;
+  float lsum = 0.f, cnt = 0.f, bad = 0.f, ssum = 0.f, val = 0.f, fsum = 0.f;
+  float Ic[CP], Sc[CP];
+#pragma unroll
+  for (int c = 0; c < CP; ++c) Ic[c] = Sc[c] = 0.f;
+  float w[CP];
+  const float wsum = class_weights<CP>(o.cw, C, w);
+  const bool focal = o.gamma > 0.f;
+  for (long p = blockIdx.x * (long)blockDim.x + threadIdx.x; p < total; p += (long)gridDim.x * blockDim.x) {
+    const long long y = labels[p];
+    if (y == ignore_index) continue;
+    if (y < 0 || y >= C) {
+      bad += 1.f;
+      continue;
+    }
+    const int n = (int)(p / ((long)Ho * Wo));
+    const int rem = (int)(p - (long)n * Ho * Wo);
+    const int r = rem / Wo, s = rem - r * Wo;
+    float z[CP];
+    full_res_logits<CP, T>(low, ld, H, W, n, r, s, sh, sw, z);
+    float m, se, zy;
+    softmax_stats<CP>(z, C, (int)y, m, se, zy, false);
+    const float inv = 1.f / se;
+    float wy = 0.f, wz = 0.f, rest = 0.f;
+#pragma unroll
+    for (int c = 0; c < CP; ++c) {
+      const bool lab = c == (int)y;
+      const float d = z[c] - m;
+      const float e = c < C ? expf(d) : 0.f;  // the padded lanes may hold anything
+      wy = lab ? w[c] : wy;
+      rest += lab ? 0.f : e;                  // sum_{c != y} e_c
+      if (c < C) wz = __builtin_fmaf(w[c], d, wz);
+      const float sc = e * inv;
+      Sc[c] += sc;
+      Ic[c] += lab ? sc : 0.f;
+    }
+    const float lse = logf(se);
+    const float nlp = m + lse - zy;  // -log pt
+    lsum = __builtin_fmaf(wy, nlp, lsum);
+    cnt += wy;
+    ssum += __builtin_fmaf(wsum, lse, -wz);
+    val += 1.f;
+    if (focal) {
+      const float omp = rest * inv;  // 1 - pt
+      const float pw = omp > 0.f ? powf(omp, o.gamma) : 0.f;
+      fsum = __builtin_fmaf(wy * pw, nlp, fsum);
+    }
+    atomicAdd(&tcnt[(int)y], 1);
+    if constexpr (EVAL) {
+      int pred = 0;
+      float best = z[0];
+#pragma unroll
+      for (int c = 1; c < CP; ++c)
+        if (c < C && z[c] > best) {  // the padded lanes C..CP-1 never compete
+          best = z[c];
+          pred = c;
+        }
+      atomicAdd(&hist[(int)y * C + pred], 1);
+    }
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  lsum = wave_sum(lsum);
+  cnt = wave_sum(cnt);
+  bad = wave_sum(bad);
+  ssum = wave_sum(ssum);
+  val = wave_sum(val);
+  fsum = wave_sum(fsum);
+  if (lane == 0) {
+    red[wave][0] = lsum; red[wave][1] = cnt; red[wave][2] = bad;
+    red[wave][3] = ssum; red[wave][4] = val; red[wave][5] = fsum;
+  }
+#pragma unroll
+  for (int c = 0; c < CP; ++c) {
+    const float vi = wave_sum(Ic[c]), vs = wave_sum(Sc[c]);
+    if (lane == 0) { red[wave][SL_FIXED + c] = vi; red[wave][SL_FIXED + CP + c] = vs; }
+  }
+  __syncthreads();  // also closes tcnt and the histogram
+  const long nb = gridDim.x;
+  if (threadIdx.x < NR) {
+    const int j = threadIdx.x;
+    const float v = red[0][j] + red[1][j] + red[2][j] + red[3][j];
+    if (j < SL_FIXED)
+      part[j * nb + blockIdx.x] = v;
+    else if (j < SL_FIXED + CP) {
+      if (j - SL_FIXED < C) part[(long)j * nb + blockIdx.x] = v;  // I_c: column 6 + c
+    } else if (j - SL_FIXED - CP < C)
+      part[(long)(j - CP + C) * nb + blockIdx.x] = v;                // S_c: column 6 + C + c
+  }
+  if (threadIdx.x < C) part[(long)(SL_FIXED + 2 * C + threadIdx.x) * nb + blockIdx.x] = (float)tcnt[threadIdx.x];
+  if constexpr (EVAL) {
+    for (int i = threadIdx.x; i < C * C; i += blockDim.x) {
+      const int v = hist[i];
+      if (v) atomicAdd(confusion + i, (unsigned long long)v);
+    }
+  }
+}
+
+// One block, four waves: each wave sums whole columns of the partials in fp64 (lane k takes blocks k, k + 64, ...,
+// then the butterfly), thread 0 forms the stats and the coefficient table from the 6 + 3 C totals.
+__global__ __launch_bounds__(256) void sl_finalize_kernel(const float* __restrict__ part, int nblk, int C, float eps,
+                                                          float ce, float dice, float gamma, float smooth,
+                                                          float* __restrict__ out, float* __restrict__ table) {
+  __shared__ double tot[SL_COLS];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int ncol = SL_FIXED + 3 * C;
+  for (int col = wave; col < ncol; col += 4) {
+    double a = 0.0;
+    for (int k = lane; k < nblk; k += 64) a += part[(long)col * nblk + k];
+    for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
+    if (lane == 0) tot[col] = a;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const double l = tot[0], d = tot[1], b = tot[2], sm = tot[3], v = tot[4], f = tot[5];
+    const double* I = tot + SL_FIXED;
+    const double* S = I + C;
+    const double* Tc = S + C;
+    int M = 0;
+    for (int c = 0; c < C; ++c) M += Tc[c] > 0.0 ? 1 : 0;
+    const double Mx = M > 0 ? (double)M : 1.0;
+    double dsum = 0.0;
+    for (int c = 0; c < CMAX; ++c) {
+      float a_c = 0.f, b_c = 0.f;
+      if (c < C && Tc[c] > 0.0) {
+        const double U = S[c] + Tc[c] + (double)smooth;
+        const double num = 2.0 * I[c] + (double)smooth;
+        dsum += 1.0 - num / U;
+        a_c = (float)(2.0 / (Mx * U));
+        b_c = (float)(num / (Mx * U * U));
+      }
+      table[c] = a_c;
+      table[CMAX + c] = b_c;
+    }
+    const double Dice = dsum / Mx;
+    const double num = gamma > 0.f ? f : eps > 0.f ? (1.0 - (double)eps) * l + ((double)eps / C) * sm : l;
+    const double F = num / d;  // 0/0 = nan when no valid pixel carries weight, as aten
+    double loss = 0.0;
+    if (ce > 0.f) loss += (double)ce * F;
+    if (dice > 0.f) loss += (double)dice * Dice;
+    out[0] = b > 0.0 ? __builtin_nanf("") : (float)loss;
+    out[1] = (float)d;
+    out[2] = (float)b;
+    out[3] = (float)v;
+    out[4] = (float)F;
+    out[5] = (float)Dice;
+  }
+}
+
+template <int CP, typename T>
+__global__ __launch_bounds__(256) void sl_up_grad_kernel(const T* __restrict__ low, long ld, int N, int H, int W,
+                                                         int C, const long long* __restrict__ labels, int Ho, int Wo,
+                                                         float sh, float sw, int ignore_index,
+                                                         const float* __restrict__ gout,
+                                                         const float* __restrict__ stats,
+                                                         const float* __restrict__ table, T* __restrict__ dhigh,
+                                                         long ldh, SlOpt o) {
+  const long total = (long)N * Ho * Wo;
+  const bool poisoned = stats[2] > 0.f, has_ce = o.ce > 0.f, has_dice = o.dice > 0.f, focal = o.gamma > 0.f;
+  const float sce = poisoned ? __builtin_nanf("") : has_ce ? gout[0] * o.ce / stats[1] : 0.f;  // (g / D) ce
+  const float sdi = poisoned ? __builtin_nanf("") : gout[0] * o.dice;                           // g dice
+  float w[CP];
+  const float wsum = class_weights<CP>(o.cw, C, w);
+  const float keep = 1.f - o.eps, spread = o.eps / (float)C;
+  for (long p = blockIdx.x * (long)blockDim.x + threadIdx.x; p < total; p += (long)gridDim.x * blockDim.x) {
+    const long long y = labels[p];
+    T* d = dhigh + p * ldh;
+    if (y == ignore_index || y < 0 || y >= C) {  // out of range: the scales are NaN, the loss already is
+#pragma unroll
+      for (int c = 0; c < CP; c += 4) st4(d + c, f32x4{0.f, 0.f, 0.f, 0.f});
+      continue;
+    }
+    const int n = (int)(p / ((long)Ho * Wo));
+    const int rem = (int)(p - (long)n * Ho * Wo);
+    const int r = rem / Wo, s = rem - r * Wo;
+    float z[CP];
+    full_res_logits<CP, T>(low, ld, H, W, n, r, s, sh, sw, z);
+    float m, se, zy;
+    softmax_stats<CP>(z, C, (int)y, m, se, zy, true);  // z[c] = e_c now
+    const float inv = 1.f / se;
+    float wy = 0.f, ey = 0.f, rest = 0.f, ay = 0.f, sb = 0.f;
+#pragma unroll
+    for (int c = 0; c < CP; ++c) {
+      const bool lab = c == (int)y;
+      wy = lab ? w[c] : wy;
+      ey = lab ? z[c] : ey;
+      rest += lab ? 0.f : z[c];
+      if (has_dice) {
+        ay = lab ? table[c] : ay;
+        sb = __builtin_fmaf(table[CMAX + c], z[c] * inv, sb);  // sum_c b_c s_c (b is 0 on the padded lanes, as e is)
+      }
+    }
+    const float omp = rest * inv, sy = ey * inv;  // 1 - pt, pt
+    const float sq = __builtin_fmaf(-ay, sy, sb);  // sum_c q_c s_c
+    float fp = 1.f;
+    if (focal) {
+      const float nlp = m + logf(se) - zy;
+      fp = omp > 0.f ? powf(omp, o.gamma) * __builtin_fmaf(o.gamma * sy, nlp / omp, 1.f) : 0.f;
+    }
+    const float kw = keep * wy * fp;
+#pragma unroll
+    for (int c = 0; c < CP; c += 4) {
+      f32x4 ov;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int cc = c + j;
+        const bool lab = cc == (int)y;
+        const float sk = z[cc] * inv;
+        const float nl = lab ? -omp : sk;  // s_k - [k = y]
+        float g = sce * __builtin_fmaf(spread, __builtin_fmaf(sk, wsum, -w[cc]), kw * nl);
+        if (has_dice) {
+          const float q = table[CMAX + cc] - (lab ? ay : 0.f);
+          g = __builtin_fmaf(sdi * sk, q - sq, g);
+        }
+        ov[j] = cc < C ? g : 0.f;
+      }
+      st4(d + c, ov);
+    }
+  }
+}
+
+template <typename T, bool EVAL>
+int sl_loss_impl(const T* low, long ld, int N, int H, int W, int C, const long long* labels, int Ho, int Wo,
+                 int ignore_index, SlOpt o, float* work, float* out6, float* table, long long* confusion,
+                 hipStream_t stream) {
+  if ((ld & 3) || C > CMAX || C < 1 || ld < C || (EVAL && !confusion) || !sl_opt_ok(o))
+    return (int)hipErrorInvalidValue;
+  const long total = (long)N * Ho * Wo;
+  const int nb = loss_blocks(total);
+  const float sh = Ho > 1 ? (float)(H - 1) / (float)(Ho - 1) : 0.f;
+  const float sw = Wo > 1 ? (float)(W - 1) / (float)(Wo - 1) : 0.f;
+#define SEG_SL_L(CP)                                                                                        \
+  case CP:                                                                                                  \
+    hipLaunchKernelGGL((sl_up_loss_kernel<CP, T, EVAL>), dim3(nb), dim3(256), 0, stream, low, ld, N, H, W,   \
+                       C, labels, Ho, Wo, sh, sw, ignore_index, work, (unsigned long long*)confusion, o);   \
+    break
+  switch ((C + 3) & ~3) {
+    SEG_SL_L(4); SEG_SL_L(8); SEG_SL_L(12); SEG_SL_L(16); SEG_SL_L(20); SEG_SL_L(24); SEG_SL_L(28); SEG_SL_L(32);
+  }
+#undef SEG_SL_L
+  hipLaunchKernelGGL(sl_finalize_kernel, dim3(1), dim3(256), 0, stream, work, nb, C, o.eps, o.ce, o.dice, o.gamma,
+                     o.smooth, out6, table);
+  SEG_RET_LAST();
+}
+
+template <typename T>
+int sl_grad_impl(const T* low, long ld, int N, int H, int W, int C, const long long* labels, int Ho, int Wo,
+                 int ignore_index, SlOpt o, const float* grad_out, const float* stats, const float* table, T* dhigh,
+                 long ldh, hipStream_t stream) {
+  if ((ld & 3) || (ldh & 3) || C > CMAX || C < 1 || ld < C || ldh < C || !sl_opt_ok(o))
+    return (int)hipErrorInvalidValue;
+  const long total = (long)N * Ho * Wo;
+  const float sh = Ho > 1 ? (float)(H - 1) / (float)(Ho - 1) : 0.f;
+  const float sw = Wo > 1 ? (float)(W - 1) / (float)(Wo - 1) : 0.f;
+  const int grid = (int)std::min<long>(seg_cdiv(total, 256), 8192);
+#define SEG_SL_G(CP)                                                                                          \
+  case CP:                                                                                                    \
+    hipLaunchKernelGGL((sl_up_grad_kernel<CP, T>), dim3(grid), dim3(256), 0, stream, low, ld, N, H, W, C,      \
+                       labels, Ho, Wo, sh, sw, ignore_index, grad_out, stats, table, dhigh, ldh, o);          \
+    break
+  switch ((C + 3) & ~3) {
+    SEG_SL_G(4); SEG_SL_G(8); SEG_SL_G(12); SEG_SL_G(16); SEG_SL_G(20); SEG_SL_G(24); SEG_SL_G(28); SEG_SL_G(32);
+  }
+#undef SEG_SL_G
+  SEG_RET_LAST();
+}
+
+}  // namespace
+
+// out6 = [loss, D, #out-of-range labels, #valid, F, Dice]; table: 64 floats (a_c at c, b_c at 32 + c), written by
+// the finalize, read by seg_sl_upsample_grad; `work` >= seg_sl_workspace_floats(N*Ho*Wo).
+SEG_API long seg_sl_workspace_floats(long pixels) { return (long)SL_COLS * loss_blocks(pixels); }
+
+SEG_API int seg_sl_upsample_loss(const float* low, long ld, int N, int H, int W, int C, const long long* labels, int Ho,
+                                 int Wo, int ignore_index, const float* class_weight, float label_smoothing, float ce,
+                                 float dice, float focal_gamma, float dice_smooth, float* work, float* out6,
+                                 float* table, hipStream_t stream) {
+  return sl_loss_impl<float, false>(low, ld, N, H, W, C, labels, Ho, Wo, ignore_index,
+                                    SlOpt{class_weight, label_smoothing, ce, dice, focal_gamma, dice_smooth}, work,
+                                    out6, table, nullptr, stream);
+}
+SEG_API int seg_sl_upsample_loss_bf16io(const __bf16* low, long ld, int N, int H, int W, int C,
+                                        const long long* labels, int Ho, int Wo, int ignore_index,
+                                        const float* class_weight, float label_smoothing, float ce, float dice,
+                                        float focal_gamma, float dice_smooth, float* work, float* out6, float* table,
+                                        hipStream_t stream) {
+  return sl_loss_impl<__bf16, false>(low, ld, N, H, W, C, labels, Ho, Wo, ignore_index,
+                                     SlOpt{class_weight, label_smoothing, ce, dice, focal_gamma, dice_smooth}, work,
+                                     out6, table, nullptr, stream);
+}
+SEG_API int seg_sl_upsample_eval(const float* low, long ld, int N, int H, int W, int C, const long long* labels, int Ho,
+                                 int Wo, int ignore_index, const float* class_weight, float label_smoothing, float ce,
+                                 float dice, float focal_gamma, float dice_smooth, float* work, float* out6,
+                                 float* table, long long* confusion, hipStream_t stream) {
+  return sl_loss_impl<float, true>(low, ld, N, H, W, C, labels, Ho, Wo, ignore_index,
+                                   SlOpt{class_weight, label_smoothing, ce, dice, focal_gamma, dice_smooth}, work,
+                                   out6, table, confusion, stream);
+}
+SEG_API int seg_sl_upsample_eval_bf16io(const __bf16* low, long ld, int N, int H, int W, int C,
+                                        const long long* labels, int Ho, int Wo, int ignore_index,
+                                        const float* class_weight, float label_smoothing, float ce, float dice,
+                                        float focal_gamma, float dice_smooth, float* work, float* out6, float* table,
+                                        long long* confusion, hipStream_t stream) {
+  return sl_loss_impl<__bf16, true>(low, ld, N, H, W, C, labels, Ho, Wo, ignore_index,
+                                    SlOpt{class_weight, label_smoothing, ce, dice, focal_gamma, dice_smooth}, work,
+                                    out6, table, confusion, stream);
+}
+SEG_API int seg_sl_upsample_grad(const float* low, long ld, int N, int H, int W, int C, const long long* labels, int Ho,
+                                 int Wo, int ignore_index, const float* class_weight, float label_smoothing, float ce,
+                                 float dice, float focal_gamma, const float* grad_out, const float* stats,
+                                 const float* table, float* dhigh, long ldh, hipStream_t stream) {
+  return sl_grad_impl(low, ld, N, H, W, C, labels, Ho, Wo, ignore_index,
+                      SlOpt{class_weight, label_smoothing, ce, dice, focal_gamma, 1.f}, grad_out, stats, table, dhigh,
+                      ldh, stream);
+}
+SEG_API int seg_sl_upsample_grad_bf16io(const __bf16* low, long ld, int N, int H, int W, int C,
+                                        const long long* labels, int Ho, int Wo, int ignore_index,
+                                        const float* class_weight, float label_smoothing, float ce, float dice,
+                                        float focal_gamma, const float* grad_out, const float* stats,
+                                        const float* table, __bf16* dhigh, long ldh, hipStream_t stream) {
+  return sl_grad_impl(low, ld, N, H, W, C, labels, Ho, Wo, ignore_index,
+                      SlOpt{class_weight, label_smoothing, ce, dice, focal_gamma, 1.f}, grad_out, stats, table, dhigh,
+                      ldh, stream);
+}

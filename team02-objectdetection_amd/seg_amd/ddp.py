@@ -6,7 +6,11 @@ none"); BASELINE.json's north_star asks for data-parallel training that shards
 the minibatch across the 8 GPUs of a node.  Semantics = PyTorch DDP without
 SyncBN: BatchNorm statistics are per rank (bs=32 each), the all-reduced
 gradient is the mean of the per-rank gradients, and (optionally) BN buffers
-are broadcast from rank 0 so eval weights are rank-independent.
+are broadcast from rank 0 so eval weights are rank-independent.  The soft Dice
+term of a seg_amd.SegLoss follows the same rule: its per-class sums I_c, S_c
+and T_c (and so the set of classes present) are per rank, each rank's Dice is
+that of its own shard, and the gradients are averaged; the sums are not
+all-reduced.
 
 Mechanism (no autograd hooks needed -- the engine IS the backward):
   * gradients live in flat per-bucket buffers (about `bucket_cap_mb` each,
@@ -334,20 +338,22 @@ class DataParallel(nn.Module):
         return self.module(x)
 
     def forward_loss(self, x, target, ignore_index: int = -100, weight=None, label_smoothing: float = 0.0,
-                     reduction: str = "mean"):
+                     reduction: str = "mean", **seg_loss):
         """The module's forward_loss on this rank's shard.  With class weights and reduction "mean"
         each rank normalises by its OWN shard's D = sum of w[label] over its valid pixels, and the
         gradients are then averaged over the ranks -- what torch's DistributedDataParallel does with
         a weighted criterion; it is not the weighted mean over the global batch unless the shards'
-        D agree."""
+        D agree.  seg_loss: seg_amd.SegLoss's ce, dice, focal_gamma, dice_smooth; its Dice sums are
+        per rank in the same way."""
         self._pre(x)
-        return self.module.forward_loss(x, target, ignore_index, weight, label_smoothing, reduction)
+        return self.module.forward_loss(x, target, ignore_index, weight, label_smoothing, reduction, **seg_loss)
 
     def forward_metrics(self, x, target, confusion, ignore_index: int = -100, weight=None,
-                        label_smoothing: float = 0.0, reduction: str = "mean"):
+                        label_smoothing: float = 0.0, reduction: str = "mean", **seg_loss):
         """Validation step of this rank's shard: no gradients, so no bucket is armed and nothing is
         broadcast; seg_amd.validate sums the ranks' matrices and losses with its own all-reduces."""
-        return self.module.forward_metrics(x, target, confusion, ignore_index, weight, label_smoothing, reduction)
+        return self.module.forward_metrics(x, target, confusion, ignore_index, weight, label_smoothing, reduction,
+                                           **seg_loss)
 
     def state_dict(self, *args, **kwargs):
         return self.module.state_dict(*args, **kwargs)

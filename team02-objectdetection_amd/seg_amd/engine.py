@@ -1200,6 +1200,8 @@ class Run:
         self.target = self.weight = self.stats = None  # labels, class weights, the [loss, count, ...] buffer
         self.label_smoothing = 0.0
         self.plain_loss = True  # no class weights, smoothing or "sum": the seg_ce_* kernels (else seg_cew_*)
+        self.sl = None          # (ce, dice, focal_gamma, dice_smooth) of a SegLoss: the seg_sl_* kernels
+        self.sl_table = None    # their per-class Dice gradient coefficients, written by the loss's finalize
 
     def k(self, name: str) -> str:
         """C-ABI entry point of an activation kernel for this run's storage type."""
@@ -1649,9 +1651,16 @@ def _check_input(x: torch.Tensor):
 REDUCTIONS = {"mean": 0, "sum": 1}  # the C ABI's `reduction` (include/segamd.h: seg_cew_*)
 
 
-def loss_options(weight, label_smoothing, reduction, C, device):
-    """The checked (weight, label_smoothing, reduction) of a fused loss over C classes on `device`; ValueError for
-    what the kernels do not take.  nn.CrossEntropyLoss's options for class-index targets, reduction "none" apart."""
+def loss_options(weight, label_smoothing, reduction, C, device, ce=1.0, dice=0.0, focal_gamma=0.0, dice_smooth=1.0):
+    """The checked (weight, label_smoothing, reduction, sl) of a fused loss over C classes on `device`; ValueError
+    for what the kernels do not take.  nn.CrossEntropyLoss's options for class-index targets, reduction "none" apart,
+    and seg_amd.SegLoss's: sl is None for plain cross-entropy (ce = 1, no Dice term, no focal exponent: the seg_ce_* /
+    seg_cew_* kernels, bitwise what they were), else (ce, dice, focal_gamma, dice_smooth) for the seg_sl_* kernels."""
+    from .losses import check_seg_loss_options
+    ce, dice, focal_gamma, dice_smooth = check_seg_loss_options(ce, dice, focal_gamma, label_smoothing, dice_smooth)
+    sl = None if (ce == 1.0 and dice == 0.0 and focal_gamma == 0.0) else (ce, dice, focal_gamma, dice_smooth)
+    if sl is not None and reduction != "mean":
+        raise ValueError(f"a Dice or focal term (or ce != 1) is defined for reduction 'mean' only, got {reduction!r}")
     if reduction not in REDUCTIONS:
         raise ValueError(f"reduction must be 'mean' or 'sum' for the fused loss, got {reduction!r}")
     eps = float(label_smoothing)
@@ -1664,23 +1673,40 @@ def loss_options(weight, label_smoothing, reduction, C, device):
                     else type(weight).__name__)
             raise ValueError(f"weight must be a contiguous float32 [{C}] tensor on {device}, got {what}")
         weight = weight.detach()
-    return weight, eps, reduction
+    return weight, eps, reduction, sl
 
 
 def _plain_loss(weight, label_smoothing, reduction):
     return weight is None and label_smoothing == 0.0 and reduction == "mean"
 
 
-def _loss_forward(run, t, ignore_index, confusion=None, weight=None, label_smoothing=0.0, reduction="mean"):
+def _loss_forward(run, t, ignore_index, confusion=None, weight=None, label_smoothing=0.0, reduction="mean", sl=None):
     """Fused final upsample + CrossEntropy over the run's low-res logits: stats = [loss, count, #bad labels].
     confusion (int64 [C, C], "metrics" mode): the same pass also adds every valid pixel to
     confusion[label, argmax] (seg_ce_upsample_eval).  With class weights, label smoothing or reduction "sum"
-    (loss_options) the seg_cew_* kernels run instead: stats = [loss, D, #bad labels, #valid], same first three slots."""
+    (loss_options) the seg_cew_* kernels run instead: stats = [loss, D, #bad labels, #valid], same first three slots.
+    sl = (ce, dice, focal_gamma, dice_smooth) of a seg_amd.SegLoss: the seg_sl_* kernels, stats = [loss, D, #bad
+    labels, #valid, F, Dice] and the table of per-class Dice gradient coefficients their gradient kernel reads."""
     prog, lo, s = run.prog, run.prog.logits, run.stream
     N = prog.N
     Ho, Wo = prog.out_hw
     run.target, run.weight, run.label_smoothing = t, weight, label_smoothing
-    run.plain_loss = _plain_loss(weight, label_smoothing, reduction)
+    run.plain_loss = sl is None and _plain_loss(weight, label_smoothing, reduction)
+    run.sl = sl
+    if sl is not None:
+        ce, dice, gamma, smooth = sl
+        stats = run.tmp(6)
+        run.sl_table = run.tmp(64)
+        work = run.tmp(query("seg_sl_workspace_floats", N * Ho * Wo))
+        args = (run.ptr(lo), lo.ld, N, lo.H, lo.W, lo.C, t.data_ptr(), Ho, Wo, ignore_index,
+                weight.data_ptr() if weight is not None else 0, label_smoothing, ce, dice, gamma, smooth,
+                work.data_ptr(), stats.data_ptr(), run.sl_table.data_ptr())
+        if confusion is None:
+            run.call(run.k("seg_sl_upsample_loss"), *args, s)
+        else:
+            run.call(run.k("seg_sl_upsample_eval"), *args, confusion.data_ptr(), s)
+        run.stats = stats
+        return stats
     if not run.plain_loss:
         stats = run.tmp(4)  # loss, D, #out-of-range labels, #valid
         work = run.tmp(query("seg_cew_workspace_floats", N * Ho * Wo))
@@ -1712,7 +1738,13 @@ def _loss_backward(run, g, ignore_index):
     Ho, Wo = prog.out_hw
     dhigh = torch.empty(max(N * Ho * Wo * lo.ld, 1), device=run.device, dtype=run.store)
     run.keep.append(dhigh)
-    if run.plain_loss:
+    if run.sl is not None:  # the forward's options (_loss_forward)
+        w = run.weight
+        ce, dice, gamma, _ = run.sl
+        run.call(run.k("seg_sl_upsample_grad"), run.ptr(lo), lo.ld, N, lo.H, lo.W, lo.C, run.target.data_ptr(), Ho,
+                 Wo, ignore_index, w.data_ptr() if w is not None else 0, run.label_smoothing, ce, dice, gamma,
+                 g.data_ptr(), run.stats.data_ptr(), run.sl_table.data_ptr(), dhigh.data_ptr(), lo.ld, s)
+    elif run.plain_loss:
         run.call(run.k("seg_ce_upsample_grad"), run.ptr(lo), lo.ld, N, lo.H, lo.W, lo.C, run.target.data_ptr(), Ho,
                  Wo, ignore_index, g.data_ptr(), run.stats.data_ptr(), dhigh.data_ptr(), lo.ld, s)
     else:  # the forward's options (_loss_forward)
@@ -1734,8 +1766,9 @@ class Plan:
     the side stream, DataParallel bucket all-reduces at host-callback stops).  Recorded
     by the first step -- a normal program walk with every launch captured instead of
     issued -- and replayed by the following ones with the caller's input / target /
-    class-weight / output / upstream-gradient pointers patched in (label smoothing and the
-    reduction are part of the plan's key; the weight VALUES are read by the kernels each step).  Buffers, workspaces, saved BN
+    class-weight / output / upstream-gradient pointers patched in (label smoothing, the
+    reduction and a SegLoss's four scalars are part of the plan's key; the weight VALUES are read by the kernels each
+    step; a SegLoss's stats and coefficient table are persistent buffers of the plan).  Buffers, workspaces, saved BN
     statistics and the flat parameter-gradient buffer are persistent (allocated while
     recording, ~13 GB at bs=32 256x512 fp32 -- nothing is recomputed).
 
@@ -1743,9 +1776,9 @@ class Plan:
     results are bitwise those of the eager engine (tests/test_gpu_tape.py)."""
 
     def __init__(self, prog, training, mode, ignore_index, sync, needs_grad, device, label_smoothing=0.0,
-                 reduction="mean"):
+                 reduction="mean", sl=None):
         self.prog, self.training, self.mode, self.ignore_index = prog, training, mode, ignore_index
-        self.label_smoothing, self.reduction = label_smoothing, reduction
+        self.label_smoothing, self.reduction, self.sl = label_smoothing, reduction, sl
         self.sync, self.needs_grad, self.device = sync, needs_grad, device
         self.side = _side_stream(device) if (OVERLAP and needs_grad) else None
         self.run = self.fwd = self.bwd = None
@@ -1805,7 +1838,8 @@ class Plan:
                 run.call(run.k("seg_upsample_to_nchw"), run.ptr(lo), lo.ld, N, lo.H, lo.W, lo.C, out.data_ptr(), Ho,
                          Wo, 1, run.stream)
             else:
-                _loss_forward(run, t, self.ignore_index, confusion, weight, self.label_smoothing, self.reduction)
+                _loss_forward(run, t, self.ignore_index, confusion, weight, self.label_smoothing, self.reduction,
+                              self.sl)
             run.rec = None
             self.run, self.fwd = run, rec.build()
         self._arm_timer(self.fwd)
@@ -1889,21 +1923,21 @@ def release_plans(model):
     model.__dict__.pop("_segamd_plans", None)
 
 
-def _plan(model, prog, mode, ignore_index, sync, needs_grad, device, opts=(None, 0.0, "mean")):
+def _plan(model, prog, mode, ignore_index, sync, needs_grad, device, opts=(None, 0.0, "mean", None)):
     """opts: loss_options().  The weight tensor itself is no part of the key (only whether there is one): its
     pointer is patched into the tapes per replay, so new weight values or a new weight tensor need no new plan."""
     cache = model.__dict__.setdefault("_segamd_plans", {})
-    weight, eps, reduction = opts
+    weight, eps, reduction, sl = opts
     # a DataParallel wrapper re-plans its buckets when the requires_grad pattern changes (its generation): the tapes
     # of an earlier generation point into buckets that are gone
     key = (id(prog), mode, model.training, ignore_index, (id(sync), sync.generation) if sync is not None else None,
-           needs_grad, OVERLAP, (eps, reduction, weight is None), plan_signature(prog))
+           needs_grad, OVERLAP, (eps, reduction, weight is None, sl), plan_signature(prog))
     fp = _fingerprint(prog)
     plan = cache.pop(key, None)  # re-inserted below: dict order = least recently used first
     if plan is None or plan.sync is not sync or plan.fp != fp:
         if plan is not None and plan.busy:
             raise RuntimeError("segamd: parameters or buffers were rebound between a forward and its backward")
-        plan = Plan(prog, model.training, mode, ignore_index, sync, needs_grad, device, eps, reduction)
+        plan = Plan(prog, model.training, mode, ignore_index, sync, needs_grad, device, eps, reduction, sl)
         plan.fp = fp
     cache[key] = plan
     while len(cache) > max(MAX_PLANS, 1):
@@ -1914,7 +1948,7 @@ def _plan(model, prog, mode, ignore_index, sync, needs_grad, device, opts=(None,
     if plan.busy:
         # a second forward before this plan's backward ran: a one-off plan keeps the first
         # forward's activations intact (recorded and run once, then dropped)
-        plan = Plan(prog, model.training, mode, ignore_index, sync, needs_grad, device, eps, reduction)
+        plan = Plan(prog, model.training, mode, ignore_index, sync, needs_grad, device, eps, reduction, sl)
         plan.fp = fp
     return plan
 
@@ -1954,7 +1988,8 @@ class _SegFunction(torch.autograd.Function):
                 raise ValueError(f"target must be int64 [{N},{Ho},{Wo}], got {tuple(t.shape)} {t.dtype}")
         needs_grad = any(ctx.needs_input_grad[7:])
         if mode == "loss":
-            opts = loss_options(*opts, prog.logits.C, x.device)
+            weight, eps, reduction, sl = opts
+            opts = loss_options(weight, eps, reduction, prog.logits.C, x.device, *(sl or ()))
         plan = _plan(model, prog, mode, ignore_index, sync, needs_grad, x.device, opts)
         out = plan.forward(x, t, weight=opts[0])
         if mode == "loss":
@@ -2049,28 +2084,33 @@ def _params_for(model, x):
 def run_logits(model, x: torch.Tensor) -> torch.Tensor:
     _check_input(x)
     sync = model.__dict__.get("_segamd_sync")
-    return _SegFunction.apply(model, "logits", x, None, IGNORE_INDEX, sync, (None, 0.0, "mean"),
+    return _SegFunction.apply(model, "logits", x, None, IGNORE_INDEX, sync, (None, 0.0, "mean", None),
                               *_params_for(model, x))
 
 
 def run_loss(model, x: torch.Tensor, target: torch.Tensor, ignore_index: int = IGNORE_INDEX, weight=None,
-             label_smoothing: float = 0.0, reduction: str = "mean") -> torch.Tensor:
-    """nn.CrossEntropyLoss(weight, ignore_index=..., reduction=..., label_smoothing=...)(model(x), target) with the
-    loss fused into the final upsample (csrc/loss.hip); the options are checked by loss_options (ValueError)."""
+             label_smoothing: float = 0.0, reduction: str = "mean", ce: float = 1.0, dice: float = 0.0,
+             focal_gamma: float = 0.0, dice_smooth: float = 1.0) -> torch.Tensor:
+    """nn.CrossEntropyLoss(weight, ignore_index=..., reduction=..., label_smoothing=...)(model(x), target), or
+    seg_amd.SegLoss(ce, dice, focal_gamma, weight, ...)(model(x), target), with the loss fused into the final upsample
+    (csrc/loss.hip); the options are checked by loss_options (ValueError)."""
     _check_input(x)
     sync = model.__dict__.get("_segamd_sync")
-    return _SegFunction.apply(model, "loss", x, target, ignore_index, sync, (weight, label_smoothing, reduction),
+    return _SegFunction.apply(model, "loss", x, target, ignore_index, sync,
+                              (weight, label_smoothing, reduction, (ce, dice, focal_gamma, dice_smooth)),
                               *_params_for(model, x))
 
 
 @torch.no_grad()
 def run_metrics(model, x: torch.Tensor, target: torch.Tensor, confusion: torch.Tensor,
                 ignore_index: int = IGNORE_INDEX, weight=None, label_smoothing: float = 0.0,
-                reduction: str = "mean") -> torch.Tensor:
+                reduction: str = "mean", ce: float = 1.0, dice: float = 0.0, focal_gamma: float = 0.0,
+                dice_smooth: float = 1.0) -> torch.Tensor:
     """Validation forward: the fused loss of run_loss, and in the same kernel
     confusion[label, argmax of the full-resolution logits] += 1 for every valid pixel
-    (csrc/loss.hip: seg_ce_upsample_eval, or seg_cew_upsample_eval with loss options -- they change
-    the returned loss only, never the matrix).  A forward tape only: no gradient is ever built, so
+    (csrc/loss.hip: seg_ce_upsample_eval, seg_cew_upsample_eval with loss options, or seg_sl_upsample_eval for a
+    SegLoss's Dice / focal terms -- they change the returned loss only, never the matrix).
+    A forward tape only: no gradient is ever built, so
     DataParallel's buckets are not involved (sync is None).  Plans are keyed by model.training
     like the others: eval() uses the running statistics, train() the batch's."""
     _check_input(x)
@@ -2087,7 +2127,7 @@ def run_metrics(model, x: torch.Tensor, target: torch.Tensor, confusion: torch.T
             or not confusion.is_contiguous()):
         raise ValueError(f"confusion must be a contiguous int64 [{C},{C}] tensor on {x.device}, got "
                          f"{tuple(confusion.shape)} {confusion.dtype} on {confusion.device}")
-    opts = loss_options(weight, label_smoothing, reduction, C, x.device)
+    opts = loss_options(weight, label_smoothing, reduction, C, x.device, ce, dice, focal_gamma, dice_smooth)
     plan = _plan(model, prog, "metrics", ignore_index, None, False, x.device, opts)
     plan.forward(x, t, confusion, opts[0])
     return _publish_stats(model, plan.run.stats)

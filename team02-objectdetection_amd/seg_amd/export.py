@@ -92,14 +92,15 @@ class TorchMobileNetV2UNet(MobileNetV2UNet):
         return torch_forward(self, x)
 
     def forward_loss(self, x, target, ignore_index: int = -100, weight=None, label_smoothing: float = 0.0,
-                     reduction: str = "mean"):
-        return nn.functional.cross_entropy(self(x), target, weight, ignore_index=ignore_index, reduction=reduction,
-                                           label_smoothing=label_smoothing)
+                     reduction: str = "mean", **seg_loss):
+        from .losses import criterion_loss
+        return criterion_loss(self(x), target, ignore_index, weight, label_smoothing, reduction, **seg_loss)
 
     def forward_metrics(self, x, target, confusion, ignore_index: int = -100, weight=None,
-                        label_smoothing: float = 0.0, reduction: str = "mean"):
+                        label_smoothing: float = 0.0, reduction: str = "mean", **seg_loss):
         from .unet import _torch_metrics
-        return _torch_metrics(self, x, target, confusion, ignore_index, weight, label_smoothing, reduction)
+        return _torch_metrics(self, x, target, confusion, ignore_index, weight, label_smoothing, reduction,
+                              **seg_loss)
 
 
 class _TorchUNetMixin:
@@ -107,14 +108,15 @@ class _TorchUNetMixin:
         return torch_forward(self, x)
 
     def forward_loss(self, x, target, ignore_index: int = -100, weight=None, label_smoothing: float = 0.0,
-                     reduction: str = "mean"):
-        return nn.functional.cross_entropy(self(x), target, weight, ignore_index=ignore_index, reduction=reduction,
-                                           label_smoothing=label_smoothing)
+                     reduction: str = "mean", **seg_loss):
+        from .losses import criterion_loss
+        return criterion_loss(self(x), target, ignore_index, weight, label_smoothing, reduction, **seg_loss)
 
     def forward_metrics(self, x, target, confusion, ignore_index: int = -100, weight=None,
-                        label_smoothing: float = 0.0, reduction: str = "mean"):
+                        label_smoothing: float = 0.0, reduction: str = "mean", **seg_loss):
         from .unet import _torch_metrics
-        return _torch_metrics(self, x, target, confusion, ignore_index, weight, label_smoothing, reduction)
+        return _torch_metrics(self, x, target, confusion, ignore_index, weight, label_smoothing, reduction,
+                              **seg_loss)
 
 
 class TorchUNet(_TorchUNetMixin, UNet):

@@ -1,0 +1,128 @@
+"""SegLoss: cross-entropy with a focal exponent, plus a soft Dice term -- the usual answers to the class imbalance
+of road scenes.
+
+Over the valid pixels V = {p : y_p != ignore_index}, with s_p = softmax(z_p) over the C classes, pt_p = s_p[y_p] and
+w = weight (all ones when None):
+
+    F    = sum_V w[y_p] (1 - pt_p)^gamma (-log pt_p) / sum_V w[y_p]
+    I_c  = sum_V s_p[c] [y_p = c],   S_c = sum_V s_p[c],   T_c = sum_V [y_p = c]
+    d_c  = (2 I_c + dice_smooth) / (S_c + T_c + dice_smooth),   m_c = [T_c > 0],   M = sum_c m_c
+    Dice = sum_c m_c (1 - d_c) / max(M, 1)
+    loss = ce F + dice Dice
+
+With gamma = 0, F is nn.CrossEntropyLoss(weight, ignore_index=..., label_smoothing=...) exactly; 0/0 is NaN, as aten.
+The Dice sums run over the whole batch, classes absent from it are left out, and the class weights do not enter
+them.  A term whose coefficient is 0 is left out of the loss (its NaN on a batch without valid pixels included).
+
+`SegLoss.forward` is this definition in torch ops: the CPU path, the path of any model without `forward_loss`, and
+the reference the fused kernels (csrc/loss.hip: seg_sl_*) are tested against.  On a seg_amd model on the GPU,
+seg_amd.train.compute_loss / validate recognise the criterion (fused_loss_options) and never build the
+full-resolution logits.
+"""
+from __future__ import annotations
+
+import math
+
+import torch
+from torch import nn
+from torch.nn import functional as F_
+
+
+def check_seg_loss_options(ce, dice, focal_gamma, label_smoothing, dice_smooth):
+    """(ce, dice, focal_gamma, dice_smooth) as floats; ValueError for what the definition excludes."""
+    ce, dice, gamma, smooth, eps = (float(ce), float(dice), float(focal_gamma), float(dice_smooth),
+                                    float(label_smoothing))
+    for name, v in (("ce", ce), ("dice", dice), ("focal_gamma", gamma)):
+        if not (math.isfinite(v) and v >= 0.0):
+            raise ValueError(f"{name} must be a finite number >= 0, got {v!r}")
+    if ce == 0.0 and dice == 0.0:
+        raise ValueError("ce and dice must not both be 0")
+    if not (math.isfinite(smooth) and smooth > 0.0):
+        raise ValueError(f"dice_smooth must be a finite number > 0, got {smooth!r}")
+    if not 0.0 <= eps <= 1.0:
+        raise ValueError(f"label_smoothing must be in [0, 1], got {label_smoothing!r}")
+    if eps > 0.0 and gamma > 0.0:
+        raise ValueError("label_smoothing > 0 together with focal_gamma > 0 is not defined")
+    return ce, dice, gamma, smooth
+
+
+def seg_loss_terms(logits, target, ce=1.0, dice=0.0, focal_gamma=0.0, weight=None, ignore_index=-100,
+                   label_smoothing=0.0, dice_smooth=1.0):
+    """(loss, F, Dice) of the module docstring for NCHW `logits` and class-index `target` [N, H, W], in torch ops.
+    A term whose coefficient is 0 is not evaluated and comes back as None."""
+    ce, dice, gamma, smooth = check_seg_loss_options(ce, dice, focal_gamma, label_smoothing, dice_smooth)
+    C = logits.shape[1]
+    valid = target != ignore_index
+    if bool((valid & ((target < 0) | (target >= C))).any()):
+        raise IndexError("Target out of bounds: label(s) outside [0, num_classes) that are not ignore_index")
+    if weight is not None:
+        weight = weight.to(logits.dtype)
+    focal = soft = None
+    if gamma > 0.0 or dice > 0.0:
+        y = torch.where(valid, target, torch.zeros_like(target)).unsqueeze(1)        # [N, 1, H, W], ignored -> 0
+        onehot = torch.zeros_like(logits, dtype=torch.bool).scatter_(1, y, True)     # [N, C, H, W]
+        s = torch.softmax(logits, 1)
+    if ce > 0.0:
+        if gamma == 0.0:
+            focal = F_.cross_entropy(logits, target, weight, ignore_index=ignore_index, reduction="mean",
+                                     label_smoothing=label_smoothing)
+        else:
+            nlp = -torch.log_softmax(logits, 1).gather(1, y).squeeze(1)              # -log pt
+            omp = s.masked_fill(onehot, 0.0).sum(1)                                  # 1 - pt as sum_{c != y} s_c
+            pw = torch.where(omp > 0, torch.where(omp > 0, omp, torch.ones_like(omp)).pow(gamma),
+                             torch.zeros_like(omp))                                  # exactly 0 where 1 - pt is 0
+            wy = (weight[y.squeeze(1)] if weight is not None else torch.ones_like(nlp)) * valid.to(nlp.dtype)
+            # where, not a product with the mask: an ignored pixel's gradient is 0 even when the quotient is 0/0
+            focal = torch.where(valid, wy * pw * nlp, torch.zeros_like(nlp)).sum() / wy.sum()
+    if dice > 0.0:
+        vm = valid.unsqueeze(1)
+        lab = onehot & vm
+        sv = s * vm.to(s.dtype)
+        I = (sv * lab.to(s.dtype)).sum((0, 2, 3))
+        S = sv.sum((0, 2, 3))
+        T = lab.sum((0, 2, 3)).to(s.dtype)
+        d = (2.0 * I + smooth) / (S + T + smooth)
+        m = (T > 0).to(s.dtype)
+        soft = ((1.0 - d) * m).sum() / m.sum().clamp(min=1.0)
+    loss = None
+    for coef, term in ((ce, focal), (dice, soft)):
+        if term is not None:
+            loss = coef * term if loss is None else loss + coef * term
+    return loss, focal, soft
+
+
+def criterion_loss(logits, target, ignore_index=-100, weight=None, label_smoothing=0.0, reduction="mean", ce=1.0,
+                   dice=0.0, focal_gamma=0.0, dice_smooth=1.0):
+    """What model.forward_loss's keyword arguments describe, on full-resolution logits in torch ops: F.cross_entropy
+    for the defaults (nn.CrossEntropyLoss's options), else SegLoss's definition (reduction "mean" only)."""
+    if float(ce) == 1.0 and float(dice) == 0.0 and float(focal_gamma) == 0.0:
+        return F_.cross_entropy(logits, target, weight, ignore_index=ignore_index, reduction=reduction,
+                                label_smoothing=label_smoothing)
+    if reduction != "mean":
+        raise ValueError(f"a Dice or focal term (or ce != 1) is defined for reduction 'mean' only, got {reduction!r}")
+    return seg_loss_terms(logits, target, ce, dice, focal_gamma, weight, ignore_index, label_smoothing,
+                          dice_smooth)[0]
+
+
+class SegLoss(nn.Module):
+    """loss = ce * F + dice * Dice (module docstring): weighted cross-entropy with label smoothing (focal_gamma = 0)
+    or its focal form (focal_gamma > 0), plus a soft Dice term over the batch.  The reduction is always the mean.
+
+    Under seg_amd.ddp.DataParallel the Dice sums are per rank, like BatchNorm statistics."""
+
+    def __init__(self, ce: float = 1.0, dice: float = 0.0, focal_gamma: float = 0.0, weight=None,
+                 ignore_index: int = -100, label_smoothing: float = 0.0, dice_smooth: float = 1.0):
+        super().__init__()
+        self.ce, self.dice, self.focal_gamma, self.dice_smooth = check_seg_loss_options(
+            ce, dice, focal_gamma, label_smoothing, dice_smooth)
+        self.ignore_index = int(ignore_index)
+        self.label_smoothing = float(label_smoothing)
+        self.register_buffer("weight", weight)
+
+    def forward(self, logits: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+        return seg_loss_terms(logits, target, self.ce, self.dice, self.focal_gamma, self.weight, self.ignore_index,
+                              self.label_smoothing, self.dice_smooth)[0]
+
+    def extra_repr(self) -> str:
+        return (f"ce={self.ce}, dice={self.dice}, focal_gamma={self.focal_gamma}, ignore_index={self.ignore_index}, "
+                f"label_smoothing={self.label_smoothing}, dice_smooth={self.dice_smooth}")

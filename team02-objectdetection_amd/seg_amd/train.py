@@ -7,7 +7,8 @@ running loss, a per-epoch "Training Loss" line and a state_dict checkpoint
 
 MI355X differences (results are the same):
   * when `criterion` is an `nn.CrossEntropyLoss` (main.py:99; class weights,
-    label smoothing and reduction "mean" / "sum" included) and the model is a
+    label smoothing and reduction "mean" / "sum" included) or a `seg_amd.SegLoss`
+    (focal exponent and soft Dice term) and the model is a
     seg_amd model, the loss is computed by the fused upsample+cross-entropy
     kernels (`model.forward_loss`), so the 168 MB of full-resolution logits
     per bs=32 batch are never written;
@@ -36,7 +37,16 @@ def fused_loss_options(criterion):
     """The keyword arguments of model.forward_loss / forward_metrics that reproduce `criterion`, or
     None when it has to run on the full-resolution logits: anything but an nn.CrossEntropyLoss
     (a subclass with a forward of its own included), and reduction="none", whose result is a
-    full-resolution tensor."""
+    full-resolution tensor.  A seg_amd.SegLoss (again without a forward of its own) adds its four
+    scalars: ce, dice, focal_gamma and dice_smooth."""
+    from .losses import SegLoss
+    if isinstance(criterion, SegLoss):
+        if type(criterion).forward is not SegLoss.forward:
+            return None
+        return {"ignore_index": criterion.ignore_index, "weight": criterion.weight,
+                "label_smoothing": float(criterion.label_smoothing), "reduction": "mean",
+                "ce": float(criterion.ce), "dice": float(criterion.dice),
+                "focal_gamma": float(criterion.focal_gamma), "dice_smooth": float(criterion.dice_smooth)}
     if not isinstance(criterion, nn.CrossEntropyLoss) or type(criterion).forward is not nn.CrossEntropyLoss.forward:
         return None
     if criterion.reduction not in ("mean", "sum"):
@@ -190,8 +200,9 @@ def validate(model, val_loader, criterion, device, progress: bool = True, epoch:
     Returns {"loss": mean of the batch means (val_loss += loss.item(); / len(val_loader)),
     "confusion", "pixel_acc", "iou", "miou"}.  The previous train/eval mode is restored.
 
-    When `criterion` is an nn.CrossEntropyLoss (fused_loss_options: class weights, label smoothing
-    and reduction "mean" / "sum" included -- they change "loss" only, never the matrix) and the
+    When `criterion` is an nn.CrossEntropyLoss or a seg_amd.SegLoss (fused_loss_options: class weights, label
+    smoothing, reduction "mean" / "sum", Dice and focal terms included -- they change "loss" only, never the
+    matrix) and the
     model has `forward_metrics`, each batch is one fused forward (loss + argmax + confusion matrix
     from the low-resolution logits); any other pair runs criterion(model(x), t) with argmax and bincount on the
     device.  Either way the batch losses and the matrix stay on the device and the host waits

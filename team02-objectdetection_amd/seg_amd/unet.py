@@ -89,41 +89,54 @@ class _SegModel(nn.Module):
         return run_logits(self, x)
 
     def forward_loss(self, x: torch.Tensor, target: torch.Tensor, ignore_index: int = -100, weight=None,
-                     label_smoothing: float = 0.0, reduction: str = "mean") -> torch.Tensor:
+                     label_smoothing: float = 0.0, reduction: str = "mean", *, ce: float = 1.0, dice: float = 0.0,
+                     focal_gamma: float = 0.0, dice_smooth: float = 1.0) -> torch.Tensor:
         """nn.CrossEntropyLoss()(self(x), target) (main.py:99, src/train.py:37) fused
         with the final upsample: the full-resolution logits are never stored.
 
         weight (float32 [C] on x's device), label_smoothing (in [0, 1]) and reduction ("mean" |
         "sum") are nn.CrossEntropyLoss's for class-index targets and stay fused; anything else
         (reduction="none" included) is a ValueError.  The weight tensor is read when the kernels
-        run: editing it in place or passing another one needs no new launch plan."""
+        run: editing it in place or passing another one needs no new launch plan.
+
+        ce, dice, focal_gamma and dice_smooth are seg_amd.SegLoss's (seg_amd/losses.py has the definition): the
+        loss becomes ce * F + dice * Dice with the focal exponent in F, fused in the same way (reduction "mean"
+        only).  The defaults are plain cross-entropy, on the code path it always took."""
         if x.device.type == "cpu":
-            return nn.functional.cross_entropy(self(x), target, weight, ignore_index=ignore_index,
-                                               reduction=reduction, label_smoothing=label_smoothing)
+            from .losses import criterion_loss
+            return criterion_loss(self(x), target, ignore_index, weight, label_smoothing, reduction, ce, dice,
+                                  focal_gamma, dice_smooth)
         from .engine import run_loss
-        return run_loss(self, x, target, ignore_index, weight, label_smoothing, reduction)
+        return run_loss(self, x, target, ignore_index, weight, label_smoothing, reduction, ce, dice, focal_gamma,
+                        dice_smooth)
 
     def forward_metrics(self, x: torch.Tensor, target: torch.Tensor, confusion: torch.Tensor,
                         ignore_index: int = -100, weight=None, label_smoothing: float = 0.0,
-                        reduction: str = "mean") -> torch.Tensor:
+                        reduction: str = "mean", *, ce: float = 1.0, dice: float = 0.0, focal_gamma: float = 0.0,
+                        dice_smooth: float = 1.0) -> torch.Tensor:
         """Validation step: returns nn.CrossEntropyLoss()(self(x), target) and adds every
         non-ignored pixel to `confusion[label, argmax(self(x))]` (int64 [C, C] on x's device, in
         place), without gradients.  On the MI355X one kernel does both from the low-resolution
-        logits: the full-resolution logits are never stored.  weight, label_smoothing and
-        reduction (as in forward_loss) change the returned loss only, never the matrix."""
+        logits: the full-resolution logits are never stored.  weight, label_smoothing, reduction and
+        SegLoss's ce, dice, focal_gamma, dice_smooth (as in forward_loss) change the returned loss only, never
+        the matrix."""
         if x.device.type == "cpu":
-            return _torch_metrics(self, x, target, confusion, ignore_index, weight, label_smoothing, reduction)
+            return _torch_metrics(self, x, target, confusion, ignore_index, weight, label_smoothing, reduction, ce,
+                                  dice, focal_gamma, dice_smooth)
         from .engine import run_metrics
-        return run_metrics(self, x, target, confusion, ignore_index, weight, label_smoothing, reduction)
+        return run_metrics(self, x, target, confusion, ignore_index, weight, label_smoothing, reduction, ce, dice,
+                           focal_gamma, dice_smooth)
 
 
 @torch.no_grad()
-def _torch_metrics(model, x, target, confusion, ignore_index, weight=None, label_smoothing=0.0, reduction="mean"):
+def _torch_metrics(model, x, target, confusion, ignore_index, weight=None, label_smoothing=0.0, reduction="mean",
+                   ce=1.0, dice=0.0, focal_gamma=0.0, dice_smooth=1.0):
     """forward_metrics in torch ops (CPU tensors): F.cross_entropy raises on an out-of-range label by itself."""
+    from .losses import criterion_loss
     from .metrics import add_confusion
     logits = model(x)
-    loss = nn.functional.cross_entropy(logits, target, weight, ignore_index=ignore_index, reduction=reduction,
-                                       label_smoothing=label_smoothing)
+    loss = criterion_loss(logits, target, ignore_index, weight, label_smoothing, reduction, ce, dice, focal_gamma,
+                          dice_smooth)
     add_confusion(confusion, logits.argmax(1), target, ignore_index)
     return loss
 
