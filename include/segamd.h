@@ -154,10 +154,23 @@ int seg_pack_conv_weight(const float* w, float* wk, int Cout, int Cin, int ks, i
                          int mode, int kin_pad, hipStream_t stream);
 
 /* Weight gradient (convolution_backward, weight path) as split-K partial slabs
- * part[splits][Cout][ks*ks*Cin]; splits from seg_conv_wgrad_splits. */
+ * part[splits][Cout][ks*ks][Cin], Cin as passed (a multiple of 4: the engine pads the stems' 3 channels with a
+ * zero one); splits from seg_conv_wgrad_splits, but any splits >= 1 is legal.
+ * Split s sums the output pixels [s * kchunk, min(M, (s + 1) * kchunk)) in NHWC row order (M = N * Ho * Wo),
+ * kchunk = ceil(M / splits) rounded up to whole K chunks: 16 pixels, the bf16-math entry points 32.  The rounding
+ * can leave trailing splits with an empty range; such a split writes an all-zero slab, so seg_conv_wgrad_reduce
+ * always sums `splits` slabs.
+ * Tile (rows of Cout x columns of Nw = ks*ks*Cin) of the launch:
+ *   Cout >= 128:       128x128 if Nw >= 128, else 128x32
+ *   64 <= Cout < 128:  64x128 if Nw >= 128, else 64x64
+ *   Cout < 64:         32x128 */
 int seg_conv_wgrad_splits(long M, int Cout, int Cin, int ks);
 /* The split count the engine uses for the bf16-math weight gradients (fewer, longer blocks). */
 int seg_conv_wgrad_splits_bf16(long M, int Cout, int Cin, int ks);
+/* The geometry seg_conv_wgrad (bf16 0) or seg_conv_wgrad_bf16 / _bf16io (bf16 1) and their _xf forms launch with
+ * for `splits` splits: out3 = {tile rows BM, tile columns BN, kchunk}.  A host function (the launch takes its tile
+ * and kchunk from the same code); hipErrorInvalidValue for arguments the launch refuses. */
+int seg_conv_wgrad_geometry(long M, int Cout, int Cin, int ks, int splits, int bf16, int* out3);
 int seg_conv_wgrad(const float* dy, long lddy, const float* x, long ldx,
                    int N, int H, int W, int Cin, int Ho, int Wo, int Cout,
                    int ks, int stride, int pad, float* part, int splits, hipStream_t stream);

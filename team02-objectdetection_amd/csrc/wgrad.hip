@@ -379,6 +379,23 @@ SEG_API int seg_conv_wgrad_splits_bf16(long M, int Cout, int Cin, int ks) {
   return wgrad_splits(M, Cout, Cin, ks, target);
 }
 
+// The split geometry of one launch, for conv_wgrad and for the seg_conv_wgrad_geometry query: the tile
+// (wgrad_tiles) and the pixels per split, ceil(M / splits) rounded up to whole K chunks (16 pixels, bf16 math 32).
+// Split s owns pixels [s * kchunk, min(M, (s + 1) * kchunk)); the rounding can leave trailing splits empty.
+static int wgrad_geometry(long M, int Cout, int Cin, int ks, int splits, bool bf, int* bm, int* bn, int* kchunk) {
+  if (M < 1 || M > INT32_MAX - SEG_WGRAD_BK_BF16 || Cout < 1 || Cin < 1 || (Cin & 3) || (ks != 1 && ks != 3) || splits < 1)
+    return (int)hipErrorInvalidValue;
+  wgrad_tiles(Cout, ks * ks * Cin, bm, bn);
+  const int bk = bf ? SEG_WGRAD_BK_BF16 : BK;
+  *kchunk = seg_cdiv(seg_cdiv(M, splits), bk) * bk;
+  return 0;
+}
+
+SEG_API int seg_conv_wgrad_geometry(long M, int Cout, int Cin, int ks, int splits, int bf16, int* out3) {
+  if (!out3) return (int)hipErrorInvalidValue;
+  return wgrad_geometry(M, Cout, Cin, ks, splits, bf16 != 0, &out3[0], &out3[1], &out3[2]);
+}
+
 // part[s][co][tap*Cin+ci] = sum over split s's pixels of dY[p][co] * X[src(p,tap)][ci].
 static int conv_wgrad(const void* dy, long lddy, const void* x, long ldx, int N, int H, int W, int Cin, int Ho,
                       int Wo, int Cout, int ks, int stride, int pad, float* part, int splits,
@@ -437,19 +454,19 @@ SEG_API int seg_conv_wgrad_bf16io_xf(const __bf16* dy, long lddy, const __bf16* 
 static int conv_wgrad(const void* dy, long lddy, const void* x, long ldx, int N, int H, int W, int Cin, int Ho,
                       int Wo, int Cout, int ks, int stride, int pad, float* part, int splits,
                       hipStream_t stream, bool bf, bool bf_io, const float* xs, const float* xb, int xact) {
-  if ((Cin & 3) || (ldx & 3) || (lddy & 3) || (ks != 1 && ks != 3) || splits < 1) return (int)hipErrorInvalidValue;
+  if ((ldx & 3) || (lddy & 3)) return (int)hipErrorInvalidValue;
   if (xs && (!xb || xact < SEG_ACT_NONE || xact > SEG_ACT_RELU6)) return (int)hipErrorInvalidValue;
   if (ks == 1 && (stride != 1 || pad != 0)) return (int)hipErrorInvalidValue;
   WgradArgs a;
+  int bm, bn;
+  // the tile and the pixels per split come from the helper the geometry query reports
+  const int rc = wgrad_geometry((long)N * Ho * Wo, Cout, Cin, ks, splits, bf || bf_io, &bm, &bn, &a.kchunk);
+  if (rc) return rc;
   a.dy = dy; a.lddy = lddy; a.x = x; a.ldx = ldx; a.part = part;
   a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.Ho = Ho; a.Wo = Wo; a.Cout = Cout;
   a.stride = stride; a.pad = pad; a.M = N * Ho * Wo; a.Nw = ks * ks * Cin;
-  a.kchunk = seg_cdiv(seg_cdiv(a.M, splits), BK) * BK;
   a.xs = xs; a.xb = xb; a.xact = xact;
-  int bm, bn;
-  wgrad_tiles(Cout, a.Nw, &bm, &bn);
   if (bf_io) {
-    a.kchunk = seg_cdiv(seg_cdiv(a.M, splits), 32) * 32;
     if (bm == 128 && bn == 128) return launch_wgrad<128, 128, 64, 64, true, __bf16>(a, ks, splits, stream);
     if (bm == 128) return launch_wgrad<128, 32, 32, 32, true, __bf16>(a, ks, splits, stream);
     if (bm == 64 && bn == 128) return launch_wgrad<64, 128, 32, 64, true, __bf16>(a, ks, splits, stream);
@@ -457,7 +474,6 @@ static int conv_wgrad(const void* dy, long lddy, const void* x, long ldx, int N,
     return launch_wgrad<32, 128, 32, 32, true, __bf16>(a, ks, splits, stream);
   }
   if (bf) {
-    a.kchunk = seg_cdiv(seg_cdiv(a.M, splits), 32) * 32;
     if (bm == 128 && bn == 128) return launch_wgrad<128, 128, 64, 64, true>(a, ks, splits, stream);
     if (bm == 128) return launch_wgrad<128, 32, 32, 32, true>(a, ks, splits, stream);
     if (bm == 64 && bn == 128) return launch_wgrad<64, 128, 32, 64, true>(a, ks, splits, stream);
