@@ -244,7 +244,32 @@ int seg_conv_wino_fused_ok(int N, int H, int W, long ldin);
  * dW = G^T [sum_t (A dY_t A^T) .* (B^T X_t B)] G.  seg_conv_wino_wgrad writes
  * fixed-order split-K partial slabs part[splits][16][Cout][Cin] (Cin = the padded
  * input channels, % 4 == 0; splits from seg_conv_wino_wgrad_splits), and
- * seg_conv_wino_wgrad_reduce sums them and writes dW [Cout][Cin_real][3][3]. */
+ * seg_conv_wino_wgrad_reduce sums them and writes dW [Cout][Cin_real][3][3].
+ * Any splits >= 1 is legal.  Split s sums the 2x2 output tiles [s * kchunk, min(T, (s + 1) * kchunk)) in
+ * (n, tile row, tile column) order, T = N * (H/2) * (W/2), kchunk = ceil(T / splits) rounded up to 16 tiles.  The
+ * rounding can leave trailing splits with an empty range; such a split writes an all-zero slab, so
+ * seg_conv_wino_wgrad_reduce always sums `splits` slabs.  Slab element [xi][co][ci], xi = 4 r + c, is
+ * sum_t (A dY_t A^T)[r][c] * (B^T X_t B)[r][c] with the matrices of csrc/wino.hip's header comment.
+ * Tile (rows of Cout x columns of Cin) of seg_conv_wino_wgrad's launch:
+ *   Cout >= 128:       128x128 if Cin >= 128, else 128x64
+ *   64 <= Cout < 128:  64x128 if Cin >= 128, else 64x64
+ *   Cout < 64:         32x128
+ * Tile (square, Cout x Cin) of seg_conv_wino_wgrad16's launch: 64 if Cin >= 128 and Cout >= 128, else 32.  A split
+ * of that kernel addresses its pixel rows with 31-bit byte offsets: where
+ * (2 * (ceil(kchunk / (W/2)) + 1) + 2) * W * max(ldx, lddy) * 4 >= 2^31 - 16 the launch is handed to
+ * seg_conv_wino_wgrad's kernel, which writes the same slabs.
+ * Column tile (output channels per block, 128 tiles each) of the 16 GEMMs of seg_conv_wino:
+ *   Cout >= 256 and ceil(Cout / 256) * 2 == ceil(Cout / 128):  256 (8 waves)
+ *   otherwise Cout >= 128:  128
+ *   Cout < 128:  64
+ * seg_conv_wino_fused has one tile (128 tiles x 32 output channels) and requires
+ * min(N, 128 / ((H/2) * (W/2)) + 2) * H * W * ldin * 4 < 2^31 - 16 (seg_conv_wino_fused_ok). */
+/* The geometry the three launchers use for this shape: out6 = {column tile of seg_conv_wino's GEMM, tile rows BM and
+ * columns BN of seg_conv_wino_wgrad, tile of seg_conv_wino_wgrad16, kchunk for `splits` splits, 1 if
+ * seg_conv_wino_wgrad16 hands the launch to the per-point kernel with ld = max(ldx, lddy), else 0}.  A host function
+ * (the launches take their tile, kchunk and that decision from the same code); hipErrorInvalidValue for arguments
+ * the launches refuse (odd H or W, Cin or Cout % 4, ld % 4, splits < 1) and for an empty problem. */
+int seg_conv_wino_geometry(int N, int H, int W, int Cin, int Cout, int splits, long ld, int* out6);
 int seg_conv_wino_wgrad_pick(int N, int H, int W, int Cin, int Cout);
 int seg_conv_wino_wgrad_splits(int N, int H, int W, int Cin, int Cout);
 int seg_conv_wino_wgrad(const float* dy, long lddy, const float* x, long ldx, int N, int H, int W, int Cin,

@@ -1028,6 +1028,59 @@ SEG_API int seg_conv_wino_row_tiles(int N, int H, int W) {
 // Pixels per BN row tile of seg_conv_wino (the tile_rows of seg_bn_stats_tiles).
 SEG_API int seg_conv_wino_tile_rows(void) { return 64 * kWinoQT; }
 
+// ---------------------------------------------------------------- launch geometry
+// The rules the three launchers and the seg_conv_wino_geometry query share (include/segamd.h states them).
+// Tiles of the problem, T = N * (H/2) * (W/2); false for a shape every entry point refuses.
+static bool wino_tiles(int N, int H, int W, int Cin, int Cout, int* T) {
+  if ((H & 1) || (W & 1) || (Cin & 3) || (Cout & 3) || N < 0 || H < 0 || W < 0) return false;
+  const long t = (long)N * (H / 2) * (W / 2);
+  if (t > INT32_MAX - 256) return false;
+  *T = (int)t;
+  return true;
+}
+// Column tile of seg_conv_wino's GEMM: the wide (8-wave, 128 x 256) tile where it pads no more columns than two
+// narrow ones (measured: Cout 256 -5..-6 %, Cout 1344 (6 x 256 = 1536 vs 11 x 128 = 1408 columns) +4 % per launch)
+static int wino_gemm_bn(int T, int Cout) {
+  if (Cout >= SEG_WINO_WIDE && seg_cdiv(Cout, 256) * 2 == seg_cdiv(Cout, 128) &&
+      (long)seg_cdiv(T, 128) * seg_cdiv(Cout, 256) * 16 >= SEG_WINO_WIDE_MINBLK)
+    return 256;
+  return Cout >= 128 ? 128 : 64;
+}
+// Tile (rows of Cout x columns of Cin) of wino_wgrad_kernel.
+static void wino_wgrad_tile(int Cin, int Cout, int* bm, int* bn) {
+  *bm = Cout >= 128 ? 128 : (Cout >= 64 ? 64 : 32);
+  *bn = *bm == 32 ? 128 : (Cin >= 128 ? 128 : 64);
+}
+// Tile (Cout x Cin, square) of wino_wgrad16_kernel.
+#ifndef SEG_WW16_WIDE
+#define SEG_WW16_WIDE 128
+#endif
+static int wgrad16_tile(int Cin, int Cout) { return (Cin >= SEG_WW16_WIDE && Cout >= SEG_WW16_WIDE) ? 64 : 32; }
+// 2x2 tiles per split of the weight gradients: ceil(T / splits) rounded up to whole K steps of the per-point kernel.
+// Split s owns tiles [s * kchunk, min(T, (s + 1) * kchunk)); the rounding can leave trailing splits empty.
+static int wino_kchunk(int T, int splits) { return seg_cdiv(seg_cdiv(T, splits), WBK) * WBK; }
+// wino_wgrad16_kernel's 31-bit buffer offsets from a split's base cover the split's pixel rows (its tile rows + the
+// halo, across image boundaries); ld = max(ldx, lddy).  Otherwise the per-point kernel writes the same slabs.
+static bool wgrad16_fits(int W, int kchunk, long ld) {
+  const long span = (2L * (seg_cdiv(kchunk, W / 2) + 1) + 2) * W * ld * 4;
+  return span < (long)kFusedOOB - 16;
+}
+
+// The geometry the launches below use: out6 = {column tile BN of seg_conv_wino's GEMM, BM and BN of
+// seg_conv_wino_wgrad, tile of seg_conv_wino_wgrad16, kchunk (tiles per split), 1 if seg_conv_wino_wgrad16 hands
+// this launch to the per-point kernel}; ld = max(ldx, lddy).  No launch.
+SEG_API int seg_conv_wino_geometry(int N, int H, int W, int Cin, int Cout, int splits, long ld, int* out) {
+  int T;
+  if (!out || !wino_tiles(N, H, W, Cin, Cout, &T) || T < 1 || Cin < 1 || Cout < 1 || splits < 1 || ld < 1 || (ld & 3))
+    return (int)hipErrorInvalidValue;
+  out[0] = wino_gemm_bn(T, Cout);
+  wino_wgrad_tile(Cin, Cout, &out[1], &out[2]);
+  out[3] = wgrad16_tile(Cin, Cout);
+  out[4] = wino_kchunk(T, splits);
+  out[5] = wgrad16_fits(W, out[4], ld) ? 0 : 1;
+  return 0;
+}
+
 // out = conv3x3(in, w) (+bias) (+add), stride 1, pad 1, by Winograd F(2x2,3x3).
 // wk: U from seg_pack_batch mode 3 (forward) / 4 (data gradient): [16][Cout][ldk],
 // ldk >= Cin.  work >= 16 * N*(H/2)*(W/2) * Cout floats.  stat (optional): BN
@@ -1035,20 +1088,17 @@ SEG_API int seg_conv_wino_tile_rows(void) { return 64 * kWinoQT; }
 SEG_API int seg_conv_wino(const float* in, long ldin, int N, int H, int W, int Cin, const float* wk, int ldk,
                           const float* bias, float* out, long ldout, int Cout, const float* add, long ldadd,
                           float* stat, float* work, hipStream_t stream) {
-  if ((H & 1) || (W & 1) || (Cin & 3) || (ldin & 3) || (ldk & 3) || ldk < Cin || (Cout & 3) || (ldout & 3) ||
+  WinoArgs a;
+  if (!wino_tiles(N, H, W, Cin, Cout, &a.T) || (ldin & 3) || (ldk & 3) || ldk < Cin || (ldout & 3) ||
       (add && (ldadd & 3)) || !work)
     return (int)hipErrorInvalidValue;
-  WinoArgs a;
   a.in = in; a.ldin = ldin; a.wk = wk; a.ldk = ldk; a.m = work;
   a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout;
-  a.th = H / 2; a.tw = W / 2; a.T = N * a.th * a.tw;
+  a.th = H / 2; a.tw = W / 2;
   if (a.T == 0) return 0;
-  // the wide tile where it pads no more columns than two narrow ones (measured: Cout 256 -5..-6 %,
-  // Cout 1344 (6 x 256 = 1536 vs 11 x 128 = 1408 columns) +4 % per launch)
-  if (Cout >= SEG_WINO_WIDE && seg_cdiv(Cout, 256) * 2 == seg_cdiv(Cout, 128) &&
-      (long)seg_cdiv(a.T, 128) * seg_cdiv(Cout, 256) * 16 >= SEG_WINO_WIDE_MINBLK)
-    launch_wino<128, 256, 64, 64, 512>(a, stream);
-  else if (Cout >= 128) launch_wino<128, 128, 64, 64>(a, stream);
+  const int bn = wino_gemm_bn(a.T, Cout);
+  if (bn == 256) launch_wino<128, 256, 64, 64, 512>(a, stream);
+  else if (bn == 128) launch_wino<128, 128, 64, 64>(a, stream);
   else launch_wino<128, 64, 64, 32>(a, stream);
   hipLaunchKernelGGL(wino_out_kernel, dim3(seg_cdiv(a.T, 16 * kWinoQT), SEG_WINO_OUT_CSPLIT ? seg_cdiv(Cout, 64) : 1), dim3(256), 0, stream, work, a.T, Cout, N, H, W, a.th,
                      a.tw, bias, add, ldadd, out, ldout, stat);
@@ -1060,14 +1110,14 @@ SEG_API int seg_conv_wino(const float* in, long ldin, int N, int H, int W, int C
 SEG_API int seg_conv_wino_fused(const float* in, long ldin, int N, int H, int W, int Cin, const float* wk, int ldk,
                                 const float* bias, float* out, long ldout, int Cout, const float* add, long ldadd,
                                 float* stat, hipStream_t stream) {
-  if ((H & 1) || (W & 1) || (Cin & 3) || (ldin & 3) || (ldk & 3) || ldk < Cin || (Cout & 3) || (add && ldadd < Cout) ||
+  WinoFusedArgs a;
+  if (!wino_tiles(N, H, W, Cin, Cout, &a.T) || (ldin & 3) || (ldk & 3) || ldk < Cin || (add && ldadd < Cout) ||
       ldout < Cout)
     return (int)hipErrorInvalidValue;
-  WinoFusedArgs a;
   a.in = in; a.ldin = ldin; a.wk = wk; a.ldk = ldk; a.bias = bias; a.add = add; a.ldadd = ldadd;
   a.out = out; a.ldout = ldout; a.stat = stat;
   a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout;
-  a.th = H / 2; a.tw = W / 2; a.T = N * a.th * a.tw;
+  a.th = H / 2; a.tw = W / 2;
   if (a.T == 0) return 0;
   const long wk_bytes = 16L * Cout * ldk * 4;
   if (!fused_fits(N, H, W, ldin) || wk_bytes >= (long)kFusedOOB) return (int)hipErrorInvalidValue;
@@ -1084,12 +1134,6 @@ SEG_API int seg_conv_wino_wgrad_pick(int N, int H, int W, int Cin, int Cout) {
   if ((H & 1) || (W & 1) || (Cin & 3) || (Cout & 3)) return 0;
   return (Cin >= 32 && Cout >= 32) ? 2 : 0;
 }
-
-// Tile (Cout x Cin, square) of wino_wgrad16_kernel.
-#ifndef SEG_WW16_WIDE
-#define SEG_WW16_WIDE 128
-#endif
-static int wgrad16_tile(int Cin, int Cout) { return (Cin >= SEG_WW16_WIDE && Cout >= SEG_WW16_WIDE) ? 64 : 32; }
 
 // Split count of seg_conv_wino_wgrad16 from a cost model fitted to tools/ww16sweep.py on MI355X: a launch runs in
 // rounds of `slots` resident blocks (256 CUs x 1 block of the 64 tile or 2 of the 32 tile); a block costs u ns per
@@ -1116,8 +1160,8 @@ SEG_API int seg_conv_wino_wgrad16_splits(int N, int H, int W, int Cin, int Cout)
 // Split count of seg_conv_wino_wgrad (partial slabs of 16 * Cout * Cin_pad floats).
 SEG_API int seg_conv_wino_wgrad_splits(int N, int H, int W, int Cin, int Cout) {
   const long T = (long)N * (H / 2) * (W / 2);
-  const int bm = Cout >= 128 ? 128 : (Cout >= 64 ? 64 : 32);
-  const int bn = bm == 32 ? 128 : (Cin >= 128 ? 128 : 64);
+  int bm, bn;
+  wino_wgrad_tile(Cin, Cout, &bm, &bn);
   const long tiles = 16L * seg_cdiv(Cout, bm) * seg_cdiv(Cin, bn);
   long splits = (2048 + tiles - 1) / tiles;
   splits = std::min(splits, std::max<long>(1, T / 128));  // >= 128 tiles (512 pixels) per split
@@ -1128,15 +1172,15 @@ SEG_API int seg_conv_wino_wgrad_splits(int N, int H, int W, int Cin, int Cout) {
 // part[splits][16][Cout][Cin] (Cin % 4 == 0: the padded input channels).
 SEG_API int seg_conv_wino_wgrad(const float* dy, long lddy, const float* x, long ldx, int N, int H, int W, int Cin,
                                 int Cout, float* part, int splits, hipStream_t stream) {
-  if ((H & 1) || (W & 1) || (Cin & 3) || (Cout & 3) || (lddy & 3) || (ldx & 3) || splits < 1)
-    return (int)hipErrorInvalidValue;
   WinoWgradArgs a;
+  if (!wino_tiles(N, H, W, Cin, Cout, &a.T) || (lddy & 3) || (ldx & 3) || splits < 1)
+    return (int)hipErrorInvalidValue;
   a.dy = dy; a.lddy = lddy; a.x = x; a.ldx = ldx; a.part = part;
   a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout;
-  a.th = H / 2; a.tw = W / 2; a.T = N * a.th * a.tw;
-  a.kchunk = seg_cdiv(seg_cdiv(a.T, splits), WBK) * WBK;
-  const int bm = Cout >= 128 ? 128 : (Cout >= 64 ? 64 : 32);
-  const int bn = bm == 32 ? 128 : (Cin >= 128 ? 128 : 64);
+  a.th = H / 2; a.tw = W / 2;
+  a.kchunk = wino_kchunk(a.T, splits);
+  int bm, bn;
+  wino_wgrad_tile(Cin, Cout, &bm, &bn);
   dim3 grid(seg_cdiv(Cout, bm) * seg_cdiv(Cin, bn) * splits, 1, 16);
   if (bm == 128 && bn == 128) hipLaunchKernelGGL((wino_wgrad_kernel<128, 128, 64, 64>), grid, dim3(256), 0, stream, a);
   else if (bm == 128) hipLaunchKernelGGL((wino_wgrad_kernel<128, 64, 64, 32>), grid, dim3(256), 0, stream, a);
@@ -1150,18 +1194,16 @@ SEG_API int seg_conv_wino_wgrad(const float* dy, long lddy, const float* x, long
 // (Cout, Cin) tile and split for all 16 transform points.
 SEG_API int seg_conv_wino_wgrad16(const float* dy, long lddy, const float* x, long ldx, int N, int H, int W, int Cin,
                                   int Cout, float* part, int splits, hipStream_t stream) {
-  if ((H & 1) || (W & 1) || (Cin & 3) || (Cout & 3) || (lddy & 3) || (ldx & 3) || splits < 1)
-    return (int)hipErrorInvalidValue;
   WinoWgradArgs a;
+  if (!wino_tiles(N, H, W, Cin, Cout, &a.T) || (lddy & 3) || (ldx & 3) || splits < 1)
+    return (int)hipErrorInvalidValue;
   a.dy = dy; a.lddy = lddy; a.x = x; a.ldx = ldx; a.part = part;
   a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout;
-  a.th = H / 2; a.tw = W / 2; a.T = N * a.th * a.tw;
-  a.kchunk = seg_cdiv(seg_cdiv(a.T, splits), WBK) * WBK;
+  a.th = H / 2; a.tw = W / 2;
   if (a.T == 0) return 0;
-  // a split's pixel rows (its tile rows + the halo, across image boundaries) must fit the kernel's 31-bit buffer
-  // offsets from its base; otherwise the per-point kernel writes the same slabs
-  const long span = (2L * (seg_cdiv(a.kchunk, a.tw) + 1) + 2) * W * std::max(ldx, lddy) * 4;
-  if (span >= (long)kFusedOOB - 16) return seg_conv_wino_wgrad(dy, lddy, x, ldx, N, H, W, Cin, Cout, part, splits, stream);
+  a.kchunk = wino_kchunk(a.T, splits);
+  if (!wgrad16_fits(W, a.kchunk, std::max(ldx, lddy)))
+    return seg_conv_wino_wgrad(dy, lddy, x, ldx, N, H, W, Cin, Cout, part, splits, stream);
   const int b = wgrad16_tile(Cin, Cout);
   const dim3 grid(seg_cdiv(Cout, b) * seg_cdiv(Cin, b) * splits);
   if (b == 64) hipLaunchKernelGGL((wino_wgrad16_kernel<64, 64, 8>), grid, dim3(256), 0, stream, a);
