@@ -741,6 +741,24 @@ int seg_grad_sumsq(const void* tensors, const long* chunks, int nchunks, int chu
 int seg_grad_scale(const void* tensors, const long* chunks, int nchunks, int chunk, const float* scale,
                    hipStream_t stream);
 
+/* ---- weight averaging (seg_amd/ema.py) over a chunk map of the same kind ------
+ * The tensor table is a device array of 24-byte records, passed as const void*:
+ *   struct SegEmaTensor {
+ *     float* ema;   the shadow (the average)
+ *     float* p;     its source: a parameter or a BatchNorm running statistic
+ *     long n;
+ *   };
+ * nchunks < 0 or chunk < 1: hipErrorInvalidValue; nchunks == 0: success, no launch. */
+/* ema = ema + one_minus_decay * (p - ema) per element in fp32 (torch.lerp's
+ * weight < 0.5 form, for every weight in [0, 1]); one_minus_decay is
+ * (float)(1 - decay) formed in double.  p is only read.  skip: as
+ * seg_adam_step_skip -- when *skip != 0 the kernel returns without touching memory. */
+int seg_ema_update(const void* tensors, const long* chunks, int nchunks, int chunk, float one_minus_decay,
+                   const float* skip, hipStream_t stream);
+/* ema[i] <-> p[i]: each element read and written by the same lane, no temporary in
+ * memory; a second call restores both sides bit for bit. */
+int seg_ema_swap(const void* tensors, const long* chunks, int nchunks, int chunk, hipStream_t stream);
+
 /* ---- launch tape (csrc/tape.hip): a recorded sequence of the launches above,
  *      replayed by one host call per segment -- the engine's training step
  *      (seg_amd/tape.py) without ~600 per-launch ctypes calls.  Not a hipGraph:

@@ -232,3 +232,74 @@ SEG_API int seg_grad_scale(const void* tensors, const long* chunks, int nchunks,
                      chunk, scale);
   SEG_RET_LAST();
 }
+
+// ---- weight averaging (seg_amd/ema.py) ---------------------------------------------------
+//
+// seg_ema_update: the exponential moving average of every floating-point state_dict entry (parameters and
+// BatchNorm running statistics) in one launch over a chunk map of the optimizer's kind:
+//   e = e + w * (p - e)                    torch.lerp(e, p, w) in its weight < 0.5 form, kept for every w in [0, 1]
+// in fp32, w = float(1 - decay) formed in double on the host, as adam_kernel's 1 - beta1.  w == 0 and p == e both
+// leave e as it is, bit for bit.  p is only read.  skip: adam_kernel's flag -- a step the device skipped is not
+// averaged in either.
+//
+// seg_ema_swap: ema[i] <-> p[i].  Each element is read and written by the same lane, so there is nothing to
+// order and no temporary in memory; two swaps restore both sides bit for bit.
+//
+// Both keep adam_kernel's walk (one 256-thread block per chunk, dword loads and stores): the pass is ~80 MB of
+// traffic that the 256 MB of last-level cache holds, beside a step of 8-16 ms (DESIGN.md has the measurement).
+struct SegEmaTensor {  // 24 bytes, the layout seg_amd/ema.py packs
+  float* ema;
+  float* p;
+  long n;
+};
+
+namespace {
+
+__global__ __launch_bounds__(256) void ema_update_kernel(const SegEmaTensor* __restrict__ ts,
+                                                         const long* __restrict__ chunks, int chunk, float w,
+                                                         const float* __restrict__ skip) {
+  if (skip && *skip != 0.f) return;  // the optimizer step was skipped: the average does not move either
+  const long ti = chunks[2 * blockIdx.x], start = chunks[2 * blockIdx.x + 1];
+  const SegEmaTensor t = ts[ti];
+  const float* __restrict__ p = t.p;
+  float* __restrict__ e = t.ema;
+  const long end = std::min<long>(t.n, start + chunk);
+  for (long i = start + threadIdx.x; i < end; i += 256) {
+    const float ev = e[i];
+    e[i] = ev + w * (p[i] - ev);
+  }
+}
+
+__global__ __launch_bounds__(256) void ema_swap_kernel(const SegEmaTensor* __restrict__ ts,
+                                                       const long* __restrict__ chunks, int chunk) {
+  const long ti = chunks[2 * blockIdx.x], start = chunks[2 * blockIdx.x + 1];
+  const SegEmaTensor t = ts[ti];
+  const long end = std::min<long>(t.n, start + chunk);
+  for (long i = start + threadIdx.x; i < end; i += 256) {
+    const float ev = t.ema[i], pv = t.p[i];
+    t.ema[i] = pv;
+    t.p[i] = ev;
+  }
+}
+
+}  // namespace
+
+// tensors: device array of SegEmaTensor (const void*: include/segamd.h documents the record); chunks / nchunks /
+// chunk as seg_adam_step_skip.  one_minus_decay: float(1 - decay) from double.  skip: as seg_adam_step_skip.
+SEG_API int seg_ema_update(const void* tensors, const long* chunks, int nchunks, int chunk, float one_minus_decay,
+                           const float* skip, hipStream_t stream) {
+  if (nchunks < 0 || chunk < 1) return (int)hipErrorInvalidValue;
+  if (nchunks == 0) return (int)hipSuccess;
+  hipLaunchKernelGGL(ema_update_kernel, dim3(nchunks), dim3(256), 0, stream, (const SegEmaTensor*)tensors, chunks,
+                     chunk, one_minus_decay, skip);
+  SEG_RET_LAST();
+}
+
+// ema[i] <-> p[i] over the table.
+SEG_API int seg_ema_swap(const void* tensors, const long* chunks, int nchunks, int chunk, hipStream_t stream) {
+  if (nchunks < 0 || chunk < 1) return (int)hipErrorInvalidValue;
+  if (nchunks == 0) return (int)hipSuccess;
+  hipLaunchKernelGGL(ema_swap_kernel, dim3(nchunks), dim3(256), 0, stream, (const SegEmaTensor*)tensors, chunks,
+                     chunk);
+  SEG_RET_LAST();
+}

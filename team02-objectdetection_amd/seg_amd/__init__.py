@@ -10,6 +10,8 @@ Public surface (drop-in for the reference's src/unet.py and src/train.py):
     Adam                                  (main.py:100's optimizer, one-launch HIP step)
     AdamW, decay_groups                   (torch.optim.AdamW as a one-launch HIP step; decayed / undecayed groups)
     grad_norm, clip_grad_norm_            (global L2 gradient norm and clipping on the device)
+    EMA                                   (exponential moving average of the weights: one launch per step,
+                                           exchanged in place with the live weights for evaluation)
     traceable                             (pure-torch CPU twin for convert.py's ONNX export)
     freeze, unfreeze, frozen_modules      (fine-tuning: frozen backbone / frozen BatchNorm statistics)
     Predictor, preprocess_image           (inference.py's per-frame path)
@@ -28,6 +30,7 @@ from .data import CombinedLaneDataset, DistributedWeightedSampler, reference_sam
 from .infer import Predictor, preprocess_image  # noqa: F401
 from .overlay import Overlay, overlay_predictions, COLOR_MAP  # noqa: F401
 from .optim import Adam, AdamW, clip_grad_norm_, decay_groups, grad_norm  # noqa: F401
+from .ema import EMA  # noqa: F401
 from .export import traceable  # noqa: F401
 from .freeze import freeze, unfreeze, frozen_modules  # noqa: F401
 
@@ -36,5 +39,5 @@ __all__ = ["MobileNetV2UNet", "UNet", "LightUNet", "double_conv", "inconv", "dow
            "synthetic_batch",
            "CombinedLaneDataset", "DistributedWeightedSampler", "reference_sample_weights",
            "Predictor", "preprocess_image", "Overlay", "overlay_predictions", "COLOR_MAP",
-           "Adam", "AdamW", "clip_grad_norm_", "decay_groups", "grad_norm",
+           "Adam", "AdamW", "clip_grad_norm_", "decay_groups", "grad_norm", "EMA",
            "traceable", "freeze", "unfreeze", "frozen_modules"]

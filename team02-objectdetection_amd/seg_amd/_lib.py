@@ -104,6 +104,8 @@ PROTOTYPES = {
     "seg_grad_norm_workspace_floats": (_L, [_I]),
     "seg_grad_sumsq": (_I, [_V, _V, _I, _I, _F, _V, _V, _V]),
     "seg_grad_scale": (_I, [_V, _V, _I, _I, _V, _V]),
+    "seg_ema_update": (_I, [_V, _V, _I, _I, _F, _V, _V]),
+    "seg_ema_swap": (_I, [_V, _V, _I, _I, _V]),
     # launch tape (csrc/tape.hip, seg_amd/tape.py)
     "seg_tape_fn_index": (_I, [ctypes.c_char_p]),
     "seg_tape_fn_nargs": (_I, [_I]),

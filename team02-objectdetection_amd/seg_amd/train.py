@@ -15,12 +15,15 @@ MI355X differences (results are the same):
   * `max_grad_norm` (not in the reference) clips the gradients' global L2 norm before
     every step; with seg_amd.Adam / seg_amd.AdamW the coefficient stays on the device
     and is applied inside the step (seg_amd/optim.py);
+  * `ema` (not in the reference) keeps an exponential moving average of the weights, one launch
+    after every step; validation and `best_checkpoint` then use the averaged model (seg_amd/ema.py);
   * under torch.distributed the gradients are averaged across ranks by
     seg_amd.ddp (RCCL all-reduce overlapped with the backward) and only
     rank 0 prints and writes checkpoints.
 """
 from __future__ import annotations
 
+import contextlib
 import os
 
 import numpy as np
@@ -94,7 +97,7 @@ def _check_labels(model, inputs):
     _raise_bad_labels(n or 0)
 
 
-def _step_and_loss(model, inputs, optimizer, loss, max_grad_norm=None):
+def _step_and_loss(model, inputs, optimizer, loss, max_grad_norm=None, ema=None):
     """optimizer.step() and loss.item() (src/train.py:39-41) with the fused loss's label check.  With seg_amd.Adam
     or seg_amd.AdamW the step is queued at once and skips itself on the device when the batch (on any rank) had an
     out-of-range label; the host reads the flag after loss.item(), whose wait covers it, and raises -- no host wait
@@ -103,7 +106,11 @@ def _step_and_loss(model, inputs, optimizer, loss, max_grad_norm=None):
     max_grad_norm: clip the global L2 norm of the gradients of the optimizer's parameters (after
     finish_gradient_sync they are the averaged ones, the same on every rank: no collective).  The two seg_amd
     optimizers take the coefficient of seg_amd.grad_norm as the step's grad_scale -- nothing waits and .grad stays
-    unclipped; any other optimizer gets seg_amd.clip_grad_norm_ in place, after the label check."""
+    unclipped; any other optimizer gets seg_amd.clip_grad_norm_ in place, after the label check.
+
+    ema: a seg_amd.EMA over the same model, updated right after the step.  Behind a step that skips itself on the
+    device it gets the same flag (a skipped step is not averaged in, still without a host wait) and its update count
+    goes back with the optimizer's before the loop raises; behind a host-side label check it is a plain update()."""
     from .optim import Adam, AdamW, clip_grad_norm_, grad_norm
     from .engine import label_flag
     flag = label_flag(model) if inputs.is_cuda else None
@@ -121,6 +128,8 @@ def _step_and_loss(model, inputs, optimizer, loss, max_grad_norm=None):
             if max_grad_norm is not None:
                 clip_grad_norm_(params, max_grad_norm)
             optimizer.step()
+        if ema is not None:
+            ema.update()
         return loss.item()
     core = getattr(model, "module", model)
     host = core.__dict__.get("_segamd_flag_host")
@@ -128,9 +137,13 @@ def _step_and_loss(model, inputs, optimizer, loss, max_grad_norm=None):
         host = core.__dict__["_segamd_flag_host"] = torch.zeros(1, dtype=torch.float32).pin_memory()
     host.copy_(flag, non_blocking=True)  # stream-ordered before the step and the loss copy below
     optimizer.step(skip_if_nonzero=flag, **(scale or {}))
+    if ema is not None:
+        ema.update(skip_if_nonzero=flag)  # the same flag: a skipped step is not averaged in
     lv = loss.item()                     # waits for this stream: the flag copy has landed
     if float(host[0]):
         optimizer.undo_step_count()      # the device skipped the step: its counters go back too
+        if ema is not None:
+            ema.undo_update_count()
         _raise_bad_labels(float(host[0]))
     return lv
 
@@ -145,10 +158,13 @@ def compute_loss(model, criterion, inputs, targets):
 
 
 def train_one_epoch(model, train_loader, criterion, optimizer, device, epoch: int = 0, epochs: int = 1,
-                    progress: bool = True, augment=None, max_grad_norm: float | None = None) -> float:
+                    progress: bool = True, augment=None, max_grad_norm: float | None = None, ema=None) -> float:
     """One pass over `train_loader`; returns the mean batch loss (src/train.py:31-44).
 
     max_grad_norm: clip the gradients' global L2 norm to it before every step (_step_and_loss); None: no clipping.
+
+    ema: a seg_amd.EMA built over `model`: updated after every optimizer step (one launch, no host wait; a step
+    skipped for an out-of-range label is not averaged in).
 
     augment: optional seg_amd.augment.GpuAugment -- the loader then yields decoded
     uint8 batches (images [N,Hs,Ws,3] RGB, masks [N,Hs,Ws] raw class ids) and the
@@ -176,7 +192,7 @@ def train_one_epoch(model, train_loader, criterion, optimizer, device, epoch: in
             sync()
         # the update never sees an out-of-range label's NaN gradients, on any rank (nn.CrossEntropyLoss raises in
         # the forward): seg_amd.Adam skips its step on the device, everything else is checked before the step
-        lv = _step_and_loss(model, inputs, optimizer, loss, max_grad_norm)
+        lv = _step_and_loss(model, inputs, optimizer, loss, max_grad_norm, ema)
         train_loss += lv
         nb += 1
         if bar is not None:
@@ -268,7 +284,8 @@ def validate(model, val_loader, criterion, device, progress: bool = True, epoch:
 def train_model(model, train_loader, criterion, optimizer, device, epochs=10,
                 checkpoint_pattern: str | None = "Models/obj/obj_MOB_1_epoch_{epoch}.pth", progress: bool = True,
                 augment=None, val_loader=None, best_checkpoint: str | None = None, freeze=None,
-                freeze_epochs: int | None = None, max_grad_norm: float | None = None):
+                freeze_epochs: int | None = None, max_grad_norm: float | None = None, ema=None,
+                ema_checkpoint_pattern: str | None = None):
     """Train for `epochs` epochs (src/train.py:6-79).  With `val_loader`, each epoch ends with the
     reference's validation phase (commented out there, src/train.py:46-76): validate(), the
     epoch's result lines, and on an improved validation loss a state_dict at `best_checkpoint`
@@ -278,7 +295,14 @@ def train_model(model, train_loader, criterion, optimizer, device, epochs=10,
     BatchNorm statistics) before the first epoch; freeze_epochs=K unfreezes it before epoch K+1, None keeps it
     frozen for the whole run.  One line is printed at each change; without `freeze` nothing changes.
 
-    max_grad_norm: train_one_epoch's -- the gradients' global L2 norm is clipped to it before every step."""
+    max_grad_norm: train_one_epoch's -- the gradients' global L2 norm is clipped to it before every step.
+
+    ema: a seg_amd.EMA built over the same model, updated after every step.  With it the per-epoch validation runs
+    on the averaged weights (under ema.applied(): the model's own plans, no copy) and `best_checkpoint` receives
+    ema.averaged_state_dict(); `ema_checkpoint_pattern` (formatted like `checkpoint_pattern`), if given, receives
+    the averaged weights every epoch.  `checkpoint_pattern`'s file keeps the live weights.  Under DataParallel every
+    rank keeps its own EMA (averaged gradients and broadcast BatchNorm statistics keep them equal without a
+    collective) and rank 0 writes the files.  One line at the start says which weights validation uses."""
     from .freeze import freeze as _freeze, unfreeze as _unfreeze
     if freeze is not None:
         if isinstance(freeze, (str, nn.Module)):
@@ -289,6 +313,11 @@ def train_model(model, train_loader, criterion, optimizer, device, epochs=10,
             names = ", ".join(f if isinstance(f, str) else type(f).__name__ for f in freeze)
             until = "the whole run" if freeze_epochs is None else f"{freeze_epochs} epoch(s)"
             print(f"Frozen for {until}: {names} (parameters and BatchNorm statistics)")
+    if ema is not None and _is_rank0():
+        print(f"EMA of the weights (decay {ema.decay:g}{', warm-up' if ema.warmup else ''}): "
+              + ("validation and best_checkpoint use the averaged weights" if val_loader is not None else
+                 "no val_loader, so nothing is validated")
+              + ("; the averaged weights are saved every epoch" if ema_checkpoint_pattern else ""))
     best_val_loss = float("inf")  # stays inf without a val_loader, as in the reference (src/train.py:46-76)
     for epoch in range(epochs):
         if freeze is not None and freeze_epochs is not None and epoch == freeze_epochs:
@@ -299,10 +328,11 @@ def train_model(model, train_loader, criterion, optimizer, device, epochs=10,
         if hasattr(sampler, "set_epoch"):
             sampler.set_epoch(epoch)  # DistributedWeightedSampler: a new shared draw per epoch
         avg_train_loss = train_one_epoch(model, train_loader, criterion, optimizer, device, epoch, epochs, progress,
-                                         augment, max_grad_norm)
+                                         augment, max_grad_norm, ema)
         val = None
         if val_loader is not None:  # every rank: validate() all-reduces
-            val = validate(model, val_loader, criterion, device, progress, epoch, epochs)
+            with ema.applied() if ema is not None else contextlib.nullcontext():
+                val = validate(model, val_loader, criterion, device, progress, epoch, epochs)
         if _is_rank0():
             if val is not None:
                 print(f"\nEpoch {epoch + 1}/{epochs}:")
@@ -313,12 +343,17 @@ def train_model(model, train_loader, criterion, optimizer, device, epochs=10,
                     print("  Validation loss improved! Saving model...")
                     if best_checkpoint:
                         os.makedirs(os.path.dirname(best_checkpoint) or ".", exist_ok=True)
-                        torch.save(getattr(model, "module", model).state_dict(), best_checkpoint)
+                        torch.save(ema.averaged_state_dict() if ema is not None else
+                                   getattr(model, "module", model).state_dict(), best_checkpoint)
             if checkpoint_pattern:
                 path = checkpoint_pattern.format(epoch=epoch + 1)
                 os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
                 core = getattr(model, "module", model)
                 torch.save(core.state_dict(), path)
+            if ema is not None and ema_checkpoint_pattern:
+                path = ema_checkpoint_pattern.format(epoch=epoch + 1)
+                os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+                torch.save(ema.averaged_state_dict(), path)
         if val is not None and val["loss"] < best_val_loss:  # every rank returns the same dict
             best_val_loss = val["loss"]
     if _is_rank0():
