@@ -541,6 +541,24 @@ int seg_preprocess_bgr(const unsigned char* frame, int N, int Hf, int Wf, long r
  * resized to the frame with cv2 INTER_NEAREST.  First maximum wins. */
 int seg_argmax_nearest(const float* low, long ld, int N, int H, int W, int C, int Hm, int Wm,
                        unsigned char* mask, int Hf, int Wf, hipStream_t stream);
+/* seg_argmax_nearest for video: the class of the exponential moving average over the frames of the
+ * per-pixel class probabilities.  Per model pixel (Hm x Wm), in fp32: z = its upsampled logits (as
+ * seg_upsample_to_nchw forms them), p = softmax(z); s = p when *fresh != 0 (or alpha == 1), else
+ * s += alpha (p - s); class = the first maximum of s, or fallback_class when that maximum < min_conf;
+ * mask = cv2 INTER_NEAREST of the classes to Hf x Wf.  A pixel with a non-finite z (a NaN or +-Inf logit
+ * among its four taps) keeps s (1/C when *fresh != 0) and is classified from it, so one bad frame does not
+ * stay in the average.
+ *   state  [N*Hm*Wm][lds] fp32, lds >= C, lds % 4 == 0, 16-byte aligned: s, read and written once per call
+ *          (lanes C..lds-1 need no initial value; those of the written quads become 0);
+ *   fresh  one device word: read by the first launch, set to 0 by the second -- the caller sets it (a
+ *          stream-ordered write) to start a new average: first frame, scene cut, seek;
+ *   labels [N][Hm][Wm] scratch: the classes at model resolution.
+ * alpha in (0, 1] (the weight of the newest frame), min_conf in [0, 1], fallback_class in [0, C), C in
+ * 1..255.  Two launches, no atomics: the same values eagerly and in a replayed graph. */
+int seg_temporal_argmax_nearest(const float* low, long ld, int N, int H, int W, int C, int Hm, int Wm,
+                                float* state, int lds, int* fresh, float alpha, float min_conf,
+                                int fallback_class, unsigned char* labels, unsigned char* mask, int Hf, int Wf,
+                                hipStream_t stream);
 
 /* ---- GPU augmentation (the readers' albumentations pipeline,
  *      src/BDD100KDataset.py:38-52) ---------------------- */

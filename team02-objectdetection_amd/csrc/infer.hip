@@ -286,6 +286,128 @@ __global__ __launch_bounds__(256) void argmax_band_kernel(const float* __restric
   }
 }
 
+// ---------------------------------------------------------------- temporal smoothing
+// One thread per MODEL pixel (its state row is read and written exactly once per frame, whatever the frame
+// size): z = the pixel's upsampled logits (model_class's taps and blend), p = softmax(z) in fp32,
+// s = p on a fresh state (*fresh != 0) or at alpha == 1, s + alpha (p - s) otherwise; a pixel with a
+// non-finite z (a NaN or +-Inf logit among its four taps) keeps s, or takes 1/C on a fresh state.  The label
+// is the first maximum of s, or `fallback` below min_conf.  NQ > 0: C's NQ channel quads stay in registers;
+// NQ == 0: any C, the blend is formed again in each of the three passes (bitwise the same values).  Pad
+// lanes C.. of the logits and of the state are loaded with their quad and never used; the state's are
+// written as 0.
+constexpr int kTemporalRegQuads = 4;
+template <int NQ>
+__global__ __launch_bounds__(64) void temporal_update_kernel(const float* __restrict__ low, long ld, int N, int H,
+                                                             int W, int C, int Hm, int Wm, float sh, float sw,
+                                                             float* __restrict__ state, int lds,
+                                                             const int* __restrict__ fresh, float alpha,
+                                                             float min_conf, int fallback,
+                                                             uint8_t* __restrict__ labels) {
+  constexpr int kUnroll = NQ ? NQ : 1;
+  const bool restart = *fresh != 0;
+  const bool replace = restart || alpha == 1.f;
+  const int nq = NQ ? NQ : (C + 3) >> 2;
+  const long total = (long)N * Hm * Wm;
+  for (long p = blockIdx.x * 64L + threadIdx.x; p < total; p += (long)gridDim.x * 64) {
+    const int n = (int)(p / ((long)Hm * Wm));
+    const int rem = (int)(p - (long)n * Hm * Wm);
+    const int ym = rem / Wm, xm = rem - ym * Wm;
+    const Lin lh = lin_index(ym, H, sh, 1), lw = lin_index(xm, W, sw, 1);
+    const float* base = low + (long)n * H * W * ld;
+    const float* t00 = base + ((long)lh.i0 * W + lw.i0) * ld;
+    const float* t01 = base + ((long)lh.i0 * W + lw.i1) * ld;
+    const float* t10 = base + ((long)lh.i1 * W + lw.i0) * ld;
+    const float* t11 = base + ((long)lh.i1 * W + lw.i1) * ld;
+    f32x4 zr[kUnroll];
+    auto logits = [&](int q) {
+      if constexpr (NQ > 0) return zr[q];
+      else return bilerp4(ld4(t00 + 4 * q), ld4(t01 + 4 * q), ld4(t10 + 4 * q), ld4(t11 + 4 * q), lh, lw);
+    };
+    if constexpr (NQ > 0) {
+#pragma unroll
+      for (int q = 0; q < NQ; ++q)
+        zr[q] = bilerp4(ld4(t00 + 4 * q), ld4(t01 + 4 * q), ld4(t10 + 4 * q), ld4(t11 + 4 * q), lh, lw);
+    }
+    // pass 1: the maximum, and whether every logit is finite
+    float zmax = -__builtin_inff();
+    bool finite = true;
+#pragma unroll kUnroll
+    for (int q = 0; q < nq; ++q) {
+      const f32x4 z = logits(q);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        if (4 * q + j >= C) continue;
+        finite = finite && fabsf(z[j]) < __builtin_inff();  // false for a NaN as well
+        zmax = fmaxf(zmax, z[j]);
+      }
+    }
+    // pass 2: the sum of exp(z - max), channels in order
+    float sum = 0.f;
+#pragma unroll kUnroll
+    for (int q = 0; q < nq; ++q) {
+      const f32x4 z = logits(q);
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (4 * q + j < C) sum += expf(z[j] - zmax);
+    }
+    // pass 3: the state row and its first maximum
+    float* srow = state + p * lds;
+    const float uniform = 1.f / (float)C;
+    float best = 0.f;
+    int arg = 0;
+#pragma unroll kUnroll
+    for (int q = 0; q < nq; ++q) {
+      const f32x4 z = logits(q);
+      f32x4 s = {0.f, 0.f, 0.f, 0.f};
+      if (!restart) s = ld4(srow + 4 * q);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int k = 4 * q + j;
+        if (k >= C) {
+          s[j] = 0.f;
+          continue;
+        }
+        if (finite) {
+          const float pk = expf(z[j] - zmax) / sum;
+          s[j] = replace ? pk : __builtin_fmaf(alpha, pk - s[j], s[j]);
+        } else if (restart) {
+          s[j] = uniform;
+        }
+        if (k == 0 || s[j] > best) {
+          best = s[j];
+          arg = k;
+        }
+      }
+      if (finite || restart) st4(srow + 4 * q, s);
+    }
+    labels[p] = (uint8_t)(best < min_conf ? fallback : arg);
+  }
+}
+
+// mask[n][yf][xf] = labels[n][nearest model pixel] (cv2 INTER_NEAREST, as argmax_nearest_kernel's): a block
+// per frame row (blockIdx.x = n * Hf + yf, its model row found once), a thread per kPix pixels of it: four
+// per 32-bit store (Wf % 4 == 0, host check) or one.  Runs after temporal_update_kernel in stream order and
+// clears the fresh word that kernel read.
+template <int kPix>
+__global__ __launch_bounds__(256) void labels_nearest_kernel(const uint8_t* __restrict__ labels, int Hm, int Wm,
+                                                             uint8_t* __restrict__ mask, int Hf, int Wf, double ify,
+                                                             double ifx, int* __restrict__ fresh) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) *fresh = 0;
+  const int n = blockIdx.x / Hf, yf = blockIdx.x - n * Hf;
+  const uint8_t* lr = labels + ((long)n * Hm + nearest_src(yf, ify, Hm)) * Wm;
+  uint8_t* out = mask + (long)blockIdx.x * Wf;
+  for (int x = threadIdx.x * kPix; x < Wf; x += 256 * kPix) {
+    if (kPix == 4) {
+      const unsigned v = (unsigned)lr[nearest_src(x, ifx, Wm)] | ((unsigned)lr[nearest_src(x + 1, ifx, Wm)] << 8) |
+                         ((unsigned)lr[nearest_src(x + 2, ifx, Wm)] << 16) |
+                         ((unsigned)lr[nearest_src(x + 3, ifx, Wm)] << 24);
+      *reinterpret_cast<unsigned*>(out + x) = v;
+    } else {
+      out[x] = lr[nearest_src(x, ifx, Wm)];
+    }
+  }
+}
+
 int grid_for(long total) { return (int)std::min<long>(seg_cdiv(total, 256), 8192); }
 
 }  // namespace
@@ -348,5 +470,43 @@ SEG_API int seg_argmax_nearest(const float* low, long ld, int N, int H, int W, i
   else
     hipLaunchKernelGGL(argmax_nearest_kernel, dim3(grid_for((long)N * Hf * Wf)), dim3(256), 0, stream, low, ld, N, H,
                        W, C, Hm, Wm, sh, sw, mask, Hf, Wf, ify, ifx);
+  SEG_RET_LAST();
+}
+
+// seg_argmax_nearest on the exponential moving average of the per-pixel class probabilities over the
+// frames of a video: state[N*Hm*Wm][lds] (fp32, model resolution) holds the average, *fresh != 0 starts a
+// new one (cleared by the second launch, so one captured graph serves the first frame and the later ones).
+// Two launches: temporal_update_kernel (state, labels[N][Hm][Wm]) and labels_nearest_kernel (mask).
+SEG_API int seg_temporal_argmax_nearest(const float* low, long ld, int N, int H, int W, int C, int Hm, int Wm,
+                                        float* state, int lds, int* fresh, float alpha, float min_conf,
+                                        int fallback_class, uint8_t* labels, uint8_t* mask, int Hf, int Wf,
+                                        hipStream_t stream) {
+  if ((ld & 3) || ld < C || (lds & 3) || lds < C || C <= 0 || C > 255 || !(alpha > 0.f && alpha <= 1.f) ||
+      !(min_conf >= 0.f && min_conf <= 1.f) || fallback_class < 0 || fallback_class >= C || !state || !fresh ||
+      !labels || ((uintptr_t)state & 15) || N <= 0 || H <= 0 || W <= 0 || Hm <= 0 || Wm <= 0 || Hf <= 0 || Wf <= 0 ||
+      (long)N * Hf > 0x7fffffffL)
+    return (int)hipErrorInvalidValue;
+  const float sh = Hm > 1 ? (float)(H - 1) / (float)(Hm - 1) : 0.f;
+  const float sw = Wm > 1 ? (float)(W - 1) / (float)(Wm - 1) : 0.f;
+  const double ify = 1.0 / ((double)Hf / Hm), ifx = 1.0 / ((double)Wf / Wm);
+  const dim3 grid((unsigned)std::min<long>(seg_cdiv((long)N * Hm * Wm, 64), 8192));
+#define SEG_TEMPORAL_UPDATE(NQ)                                                                                 \
+  hipLaunchKernelGGL(temporal_update_kernel<NQ>, grid, dim3(64), 0, stream, low, ld, N, H, W, C, Hm, Wm, sh, sw, \
+                     state, lds, fresh, alpha, min_conf, fallback_class, labels)
+  static_assert(kTemporalRegQuads == 4, "one case per register variant");
+  switch ((C + 3) / 4) {
+    case 1: SEG_TEMPORAL_UPDATE(1); break;
+    case 2: SEG_TEMPORAL_UPDATE(2); break;
+    case 3: SEG_TEMPORAL_UPDATE(3); break;
+    case 4: SEG_TEMPORAL_UPDATE(4); break;
+    default: SEG_TEMPORAL_UPDATE(0); break;
+  }
+#undef SEG_TEMPORAL_UPDATE
+  if (Wf % 4 == 0 && ((uintptr_t)mask & 3) == 0)
+    hipLaunchKernelGGL(labels_nearest_kernel<4>, dim3(N * Hf), dim3(256), 0, stream, labels, Hm, Wm, mask, Hf, Wf, ify,
+                       ifx, fresh);
+  else
+    hipLaunchKernelGGL(labels_nearest_kernel<1>, dim3(N * Hf), dim3(256), 0, stream, labels, Hm, Wm, mask, Hf, Wf, ify,
+                       ifx, fresh);
   SEG_RET_LAST();
 }

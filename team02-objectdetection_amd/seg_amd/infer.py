@@ -15,11 +15,15 @@ captured once into a HIP graph (torch.cuda.CUDAGraph drives hipGraph on ROCm):
                             (Program.fold: one seg_bn_fold_batch + one seg_pack_batch)
     seg_argmax_nearest      final align_corners=True upsample + argmax + nearest
                             resize to the frame -> uint8 class mask
+                            (seg_temporal_argmax_nearest with `temporal=` / `min_confidence=`:
+                            the argmax of the class probabilities averaged over the frames)
 
 `preprocess_image` mirrors inference.py's function of the same name (same
 argument meaning and return values) for callers that still want the tensor.
 """
 from __future__ import annotations
+
+import numbers
 
 import numpy as np
 import torch
@@ -55,6 +59,27 @@ def preprocess_image(image, target_size=(256, 128), device="cuda"):
     return img, None
 
 
+def temporal_options(temporal, min_confidence=0.0, fallback_class=0, classes=None):
+    """Validate Predictor's smoothing options.  Returns None when the feature is off (temporal None and
+    min_confidence 0), else (alpha, min_confidence, fallback_class) as seg_temporal_argmax_nearest takes
+    them; alpha is 1.0 (no smoothing) when only min_confidence is given.  `classes`: the model's class
+    count, when known, bounds fallback_class."""
+    def number(v):
+        return isinstance(v, numbers.Real) and not isinstance(v, bool)
+
+    if temporal is not None and not (number(temporal) and 0.0 < temporal <= 1.0):
+        raise ValueError(f"Predictor temporal must be None or the newest frame's weight in (0, 1], got {temporal!r}")
+    if not (number(min_confidence) and 0.0 <= min_confidence <= 1.0):
+        raise ValueError(f"Predictor min_confidence must lie in [0, 1], got {min_confidence!r}")
+    if not isinstance(fallback_class, numbers.Integral) or isinstance(fallback_class, bool) or fallback_class < 0:
+        raise ValueError(f"Predictor fallback_class must be a class index >= 0, got {fallback_class!r}")
+    if classes is not None and fallback_class >= classes:
+        raise ValueError(f"Predictor fallback_class {fallback_class} is not one of the model's {classes} classes")
+    if temporal is None and min_confidence == 0:
+        return None
+    return (1.0 if temporal is None else float(temporal)), float(min_confidence), int(fallback_class)
+
+
 class Predictor:
     """Frame -> class mask for a MobileNetV2UNet / UNet in eval mode.
 
@@ -69,10 +94,18 @@ class Predictor:
     overlay=True (or an `Overlay` instance) appends overlay_predictions' post-processing
     (seg_amd/overlay.py) to the launch sequence and the graph:
     result, detected_objects = predictor.annotate(frame); `__call__` still returns the mask.
+
+    temporal=alpha (0 < alpha <= 1) classifies video: the mask is the argmax of an exponential moving
+    average of the per-pixel class probabilities, s += alpha (softmax(logits) - s), kept at model
+    resolution across frames (seg_temporal_argmax_nearest in place of seg_argmax_nearest, inside the
+    graph too); min_confidence > 0 paints pixels whose largest averaged probability is below it with
+    fallback_class.  Either option switches the path on (alpha 1.0 when only min_confidence is given).
+    `reset()` starts a new average (scene cut, seek); `probabilities()` / `confidence()` read it.
     """
 
     def __init__(self, model, frame_hw=(720, 1280), target_size=(256, 128), graph: bool = True, math: str = "f32",
-                 overlay=False):
+                 overlay=False, temporal: float | None = None, min_confidence: float = 0.0, fallback_class: int = 0):
+        temporal_options(temporal, min_confidence, fallback_class)  # bad values: ValueError before anything else
         p = next(model.parameters())
         if not p.is_cuda:
             raise RuntimeError("Predictor runs on the MI355X HIP path only; move the model to 'cuda' first")
@@ -89,6 +122,14 @@ class Predictor:
         self.mask = torch.empty((self.Hf, self.Wf), device=self.device, dtype=torch.uint8)
         self.run = Run(self.prog, self.frame, training=False)
         self.classes = self.prog.logits.C
+        self.temporal = temporal_options(temporal, min_confidence, fallback_class, self.classes)
+        if self.temporal is not None:
+            Ho, Wo = self.prog.out_hw
+            lds = (self.classes + 3) // 4 * 4
+            # the average [Ho*Wo][lds], the word that starts a new one, the classes at model resolution
+            self._state = torch.zeros((Ho * Wo, lds), device=self.device, dtype=torch.float32)
+            self._fresh = torch.ones(1, device=self.device, dtype=torch.int32)
+            self._labels = torch.zeros((Ho, Wo), device=self.device, dtype=torch.uint8)
         self.graph = None
         self.refresh()
         self.stem_pre = self.prog.stem_pre() if (engine.STEM_PRE and math == "f16") else None
@@ -100,6 +141,8 @@ class Predictor:
                 raise ValueError(f"overlay must be True or an Overlay for {self.Hf}x{self.Wf} frames")
         if graph:
             self._capture()
+            if self.temporal is not None:
+                self.reset()  # the warm-up launch of the capture averaged the empty frame buffer
 
     def refresh(self):
         """Re-fold BatchNorm into the conv weights (after weights/statistics change)."""
@@ -122,8 +165,14 @@ class Predictor:
             rt.forward_folded()
         lo = prog.logits
         Ho, Wo = prog.out_hw
-        call("seg_argmax_nearest", rt.ptr(lo), lo.ld, 1, lo.H, lo.W, lo.C, Ho, Wo, self.mask.data_ptr(), self.Hf,
-             self.Wf, s)
+        if self.temporal is None:
+            call("seg_argmax_nearest", rt.ptr(lo), lo.ld, 1, lo.H, lo.W, lo.C, Ho, Wo, self.mask.data_ptr(), self.Hf,
+                 self.Wf, s)
+        else:
+            alpha, min_conf, fallback = self.temporal
+            call("seg_temporal_argmax_nearest", rt.ptr(lo), lo.ld, 1, lo.H, lo.W, lo.C, Ho, Wo,
+                 self._state.data_ptr(), self._state.shape[1], self._fresh.data_ptr(), alpha, min_conf, fallback,
+                 self._labels.data_ptr(), self.mask.data_ptr(), self.Hf, self.Wf, s)
         if self.overlay is not None:
             self.overlay.launch(self.frame, self.mask, s)
 
@@ -170,6 +219,24 @@ class Predictor:
             raise RuntimeError("annotate() needs Predictor(..., overlay=True)")
         self(frame)
         return self.overlay.result, self.overlay.detected_objects()
+
+    def reset(self):
+        """Start a new average with the next frame (a scene cut, a seek): sets the device word the update
+        kernel reads, in stream order; the captured graph stays as it is.  refresh() does not reset."""
+        if self.temporal is None:
+            raise RuntimeError("reset() needs Predictor(..., temporal=alpha) or min_confidence > 0")
+        self._fresh.fill_(1)
+
+    def probabilities(self) -> torch.Tensor:
+        """[1, C, H, W] float32 view of the averaged class probabilities s_t after the last frame."""
+        if self.temporal is None:
+            raise RuntimeError("probabilities() needs Predictor(..., temporal=alpha) or min_confidence > 0")
+        Ho, Wo = self.prog.out_hw
+        return self._state.view(1, Ho, Wo, -1)[..., :self.classes].permute(0, 3, 1, 2)
+
+    def confidence(self) -> torch.Tensor:
+        """[H, W] float32: the largest averaged class probability of every model pixel."""
+        return self.probabilities()[0].amax(dim=0)
 
     def logits(self) -> torch.Tensor:
         """[1, C, H, W] logits of the last frame (the model's return value, src/unet.py:49)."""
