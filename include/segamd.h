@@ -515,6 +515,45 @@ int seg_sl_upsample_grad(const float* low, long ld, int N, int H, int W, int C,
                          const float* class_weight, float label_smoothing, float ce, float dice,
                          float focal_gamma, const float* grad_out, const float* stats,
                          const float* table, float* dhigh, long ldh, hipStream_t stream);
+/* seg_amd.OhemCELoss: cross-entropy with online hard example mining, fused with the same upsample
+ * (the full-resolution logits never stored, no float atomics, no host wait).  Over the valid
+ * pixels V, with l_p = lse_p - z_p[y_p] (unweighted), w = class_weight (ones when NULL),
+ * tau = loss_thresh = -log(thresh) and k = min(min_kept, |V|):
+ *   lambda = the k-th largest l_p over V,   K = {p in V : l_p > tau or l_p >= lambda},
+ *   D = sum_K w[y_p],   loss = sum_K w[y_p] l_p / D,
+ *   dloss/dz_p[c] = g / D w[y_p] (softmax_c - [c == y_p]) for p in K, exactly 0 elsewhere.
+ * A tie group at lambda is kept whole, so K depends on neither the pixel order nor the thread
+ * mapping.  lambda is found exactly by a three-level radix select (11 / 10 / 10 bits) over the bit
+ * patterns of the l_p, which are >= 0: integer histograms only, a fixed launch sequence, and two
+ * calls on the same inputs agree bitwise.
+ * out6 = [loss, D, #labels outside [0, C) that are not ignore_index, #valid pixels, #kept pixels,
+ * cut = min(tau, lambda)]: the first three slots mean what they mean in seg_cew_*.  No pixel kept
+ * (none valid) gives NaN (0/0, as aten); an out-of-range label makes the loss and every gradient
+ * NaN.  _eval adds the confusion matrix of seg_ce_upsample_eval, over all valid pixels, not over K.
+ * `work` >= seg_ohem_workspace_floats(N*Ho*Wo) floats; its histograms and counters are cleared on
+ * the stream by every call.  Its first N*Ho*Wo floats are the per-pixel losses l_p in pixel order
+ * (-1 where the label is ignore_index or out of range); _grad reads them and lambda back from the
+ * `work` of the _loss / _eval call whose out6 is its `stats`, and never recomputes the keep decision.  On K its rows
+ * are what seg_cew_upsample_grad writes for the labels with every pixel outside K ignored.
+ * seg_ohem_upsample_grad_bf16io writes the full-resolution gradient as fp32 NCHW [N][C][Ho][Wo] (no `ldh`; follow
+ * with seg_upsample_bwd_bf16io(nchw_grad = 1)): the low-resolution gradient then sums unrounded terms, as behind the
+ * model's full-resolution logits, where bf16 rows would put 2^-9 on every term.
+ * hipErrorInvalidValue before any launch: C outside [1, 32], ld (ldh) % 4 != 0 or < C, min_kept < 1,
+ * loss_thresh negative or not finite, N*Ho*Wo >= 2^31, or (_eval) confusion NULL. */
+long seg_ohem_workspace_floats(long pixels);
+int seg_ohem_upsample_loss(const float* low, long ld, int N, int H, int W, int C,
+                           const long long* labels, int Ho, int Wo, int ignore_index,
+                           const float* class_weight, float loss_thresh, long min_kept,
+                           float* work, float* out6, hipStream_t stream);
+int seg_ohem_upsample_eval(const float* low, long ld, int N, int H, int W, int C,
+                           const long long* labels, int Ho, int Wo, int ignore_index,
+                           const float* class_weight, float loss_thresh, long min_kept,
+                           float* work, float* out6, long long* confusion, hipStream_t stream);
+int seg_ohem_upsample_grad(const float* low, long ld, int N, int H, int W, int C,
+                           const long long* labels, int Ho, int Wo, int ignore_index,
+                           const float* class_weight, float loss_thresh, const float* work,
+                           const float* grad_out, const float* stats, float* dhigh, long ldh,
+                           hipStream_t stream);
 
 /* ---- inference (inference.py: preprocess_image :28-46, model.eval() forward
  *      :23-25,162-163, overlay_predictions' argmax + resize :64-70) ---------- */
@@ -656,6 +695,15 @@ int seg_sl_upsample_grad_bf16io(const seg_bf16* low, long ld, int N, int H, int 
     Ho, int Wo, int ignore_index, const float* class_weight, float label_smoothing, float ce, float dice, float
     focal_gamma, const float* grad_out, const float* stats, const float* table, seg_bf16* dhigh, long ldh, hipStream_t
     stream);
+int seg_ohem_upsample_loss_bf16io(const seg_bf16* low, long ld, int N, int H, int W, int C, const long long* labels,
+    int Ho, int Wo, int ignore_index, const float* class_weight, float loss_thresh, long min_kept, float* work, float*
+    out6, hipStream_t stream);
+int seg_ohem_upsample_eval_bf16io(const seg_bf16* low, long ld, int N, int H, int W, int C, const long long* labels,
+    int Ho, int Wo, int ignore_index, const float* class_weight, float loss_thresh, long min_kept, float* work, float*
+    out6, long long* confusion, hipStream_t stream);
+int seg_ohem_upsample_grad_bf16io(const seg_bf16* low, long ld, int N, int H, int W, int C, const long long* labels,
+    int Ho, int Wo, int ignore_index, const float* class_weight, float loss_thresh, const float* work, const float*
+    grad_out, const float* stats, float* dhigh_nchw, hipStream_t stream);
 int seg_upsample_fwd_bf16io(const seg_bf16* in, long ldin, int N, int H, int W, int C, seg_bf16* out, long ldout, int
     Ho, int Wo, int ac, hipStream_t stream);
 int seg_upsample_bwd_bf16io(const void* dout, long ldout, int nchw_grad, int N, int Ho, int Wo, int C, seg_bf16* din,

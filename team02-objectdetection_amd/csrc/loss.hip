@@ -851,3 +851,424 @@ SEG_API int seg_sl_upsample_grad_bf16io(const __bf16* low, long ld, int N, int H
                       SlOpt{class_weight, label_smoothing, ce, dice, focal_gamma, 1.f}, grad_out, stats, table, dhigh,
                       ldh, stream);
 }
+
+// ---- online hard example mining: seg_ohem_* (the criterion is seg_amd.OhemCELoss) ----
+// Over the valid pixels V, with l_p = lse_p - z_p[y_p] the unweighted cross-entropy, tau = -log(thresh) and
+// k = min(min_kept, |V|):
+//   lambda = the k-th largest l_p over V,   K = {p in V : l_p > tau or l_p >= lambda}   (a tie group at lambda whole),
+//   D = sum_K w[y_p],   loss = sum_K w[y_p] l_p / D,   d loss / d z_p = g w[y_p] (softmax(z_p) - onehot(y_p)) / D on K, 0 elsewhere.
+// l_p >= 0 in fp32 (se >= 1 and m >= z_y, every rounding monotone), so its low 31 bits are an unsigned key in the
+// order of the values, and lambda is found exactly by a radix select over three digits of 11 / 10 / 10 bits:
+//   1. the loss pass stores l_p (4 B per pixel, -1 for an ignored or out-of-range label) at the front of `work`,
+//      counts #valid, #out-of-range and #{l_p > tau}, and histograms the top digit (per-block LDS histogram, its
+//      non-zero bins added to the global one: integer atomics only, so the sums do not depend on arrival order);
+//   2. two refine passes over the 4 B per pixel: every block finds the bin of the k-th largest in the last
+//      histogram for itself (one scan of <= 2048 counters from L2, the same result in every block; block 0 leaves it
+//      in `work` for the next launch) and histograms the next digit of the pixels in that bin.  When #{l_p > tau}
+//      already reaches k, K = {l_p > tau} and lambda is not needed: both passes return at once (the launch
+//      sequence is fixed, the tape replays it);
+//   3. the reduce pass picks the last digit -- lambda is exact -- and sums w[y] l and w[y] over K into per-block
+//      partials in a fixed order; one fp64 finalize writes stats = [loss, D, #out-of-range, #valid, #kept, cut],
+//      cut = min(tau, lambda).
+// The gradient kernel has the plain one's grid and expressions and reads the keep decision from the stored l_p, tau
+// and lambda (in `work`; +inf in threshold mode), so forward and backward agree on K by construction.
+// work: [pixels] l_p | OH_CTL words of histograms and counters (cleared on the stream by every call) | 2 floats per block.
+namespace {
+
+constexpr int OH_B0 = 2048, OH_B1 = 1024, OH_B2 = 1024;  // bins of key >> 20, (key >> 10) & 1023, key & 1023
+constexpr int OH_H1 = OH_B0, OH_H2 = OH_B0 + OH_B1, OH_CNT = OH_B0 + OH_B1 + OH_B2;
+// counters behind the histograms: #valid, #out-of-range, #{l > tau}, #kept, then the select's state
+enum { OH_VALID = 0, OH_BAD, OH_ABOVE, OH_KEPT, OH_BIN0, OH_NEED0, OH_BIN1, OH_NEED1, OH_LAMBDA, OH_NCNT = 16 };
+constexpr int OH_CTL = OH_CNT + OH_NCNT;
+constexpr unsigned OH_INF = 0x7f800000u;
+
+__device__ __forceinline__ unsigned oh_key(float l) { return __float_as_uint(l) & 0x7fffffffu; }
+__device__ __forceinline__ bool oh_valid(float l) { return l != -1.f; }
+__device__ __forceinline__ bool oh_keep(float l, float tau, float lambda) { return l > tau || l >= lambda; }
+
+// k = min(min_kept, #valid); threshold mode (nothing to select) when no pixel is valid or #{l > tau} >= k
+__device__ __forceinline__ bool oh_select(const unsigned* __restrict__ cnt, long min_kept, unsigned& k) {
+  const unsigned nv = cnt[OH_VALID];
+  k = (unsigned)(min_kept < (long)nv ? min_kept : (long)nv);
+  return nv > 0 && cnt[OH_ABOVE] < k;
+}
+
+// Block-wide (256 threads): the bin of the need-th largest entry of hist[NB] (1 <= need <= its total), counted from
+// the top bin down, and the rank that is left inside that bin.  s: 6 words of LDS.
+template <int NB>
+__device__ __forceinline__ void oh_pick(const unsigned* __restrict__ hist, unsigned need, unsigned* s, unsigned& bin,
+                                        unsigned& rest) {
+  constexpr int PER = NB / 256;
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  unsigned c[PER], sum = 0;
+#pragma unroll
+  for (int j = 0; j < PER; ++j) {
+    c[j] = hist[NB - 1 - (t * PER + j)];
+    sum += c[j];
+  }
+  unsigned incl = sum;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const unsigned v = __shfl_up(incl, o, 64);
+    if (lane >= o) incl += v;
+  }
+  if (t == 0) { s[4] = 0; s[5] = 1; }
+  if (lane == 63) s[wave] = incl;
+  __syncthreads();
+  for (int w = 0; w < wave; ++w) incl += s[w];
+  unsigned acc = incl - sum;
+  if (acc < need && need <= incl) {
+#pragma unroll
+    for (int j = 0; j < PER; ++j) {
+      if (acc < need && need <= acc + c[j]) { s[4] = NB - 1 - (t * PER + j); s[5] = need - acc; }
+      acc += c[j];
+    }
+  }
+  __syncthreads();
+  bin = s[4];
+  rest = s[5];
+  __syncthreads();
+}
+
+// EVAL: also the confusion matrix of seg_ce_upsample_eval (over all valid pixels, not over K).
+template <int CP, typename T, bool EVAL>
+__global__ __launch_bounds__(256) void oh_up_loss_kernel(const T* __restrict__ low, long ld, int N, int H, int W,
+                                                         int C, const long long* __restrict__ labels, int Ho, int Wo,
+                                                         float sh, float sw, int ignore_index, float tau,
+                                                         float* __restrict__ lbuf, unsigned* __restrict__ ctl,
+                                                         unsigned long long* __restrict__ confusion) {
+  __shared__ unsigned h0[OH_B0];
+  __shared__ unsigned cnt[3];
+  __shared__ int hist[EVAL ? CMAX * CMAX : 1];
+  for (int i = threadIdx.x; i < OH_B0; i += blockDim.x) h0[i] = 0;
+  if (threadIdx.x < 3) cnt[threadIdx.x] = 0;
+  if constexpr (EVAL)
+    for (int i = threadIdx.x; i < C * C; i += blockDim.x) hist[i] = 0;
+  __syncthreads();
+  const long total = (long)N * Ho * Wo;
+  unsigned nvalid = 0, nbad = 0, nabove = 0;
+  for (long p = blockIdx.x * (long)blockDim.x + threadIdx.x; p < total; p += (long)gridDim.x * blockDim.x) {
+    const long long y = labels[p];
+    if (y == ignore_index || y < 0 || y >= C) {
+      nbad += y == ignore_index ? 0u : 1u;
+      lbuf[p] = -1.f;
+      continue;
+    }
+    const int n = (int)(p / ((long)Ho * Wo));
+    const int rem = (int)(p - (long)n * Ho * Wo);
+    const int r = rem / Wo, s = rem - r * Wo;
+    float z[CP];
+    full_res_logits<CP, T>(low, ld, H, W, n, r, s, sh, sw, z);
+    float m, se, zy;
+    softmax_stats<CP>(z, C, (int)y, m, se, zy, false);
+    const float l = m + logf(se) - zy;  // the plain kernel's per-pixel term
+    lbuf[p] = l;
+    nvalid += 1u;
+    nabove += l > tau ? 1u : 0u;
+    atomicAdd(&h0[oh_key(l) >> 20], 1u);
+    if constexpr (EVAL) {
+      int pred = 0;
+      float best = z[0];
+#pragma unroll
+      for (int c = 1; c < CP; ++c)
+        if (c < C && z[c] > best) {  // the padded lanes C..CP-1 never compete
+          best = z[c];
+          pred = c;
+        }
+      atomicAdd(&hist[(int)y * C + pred], 1);
+    }
+  }
+  if (nvalid) atomicAdd(&cnt[0], nvalid);
+  if (nbad) atomicAdd(&cnt[1], nbad);
+  if (nabove) atomicAdd(&cnt[2], nabove);
+  __syncthreads();
+  for (int i = threadIdx.x; i < OH_B0; i += blockDim.x) {
+    const unsigned v = h0[i];
+    if (v) atomicAdd(ctl + i, v);
+  }
+  if (threadIdx.x < 3 && cnt[threadIdx.x]) atomicAdd(ctl + OH_CNT + threadIdx.x, cnt[threadIdx.x]);
+  if constexpr (EVAL) {
+    for (int i = threadIdx.x; i < C * C; i += blockDim.x) {
+      const int v = hist[i];
+      if (v) atomicAdd(confusion + i, (unsigned long long)v);
+    }
+  }
+}
+
+// LEVEL 1: pick the top digit's bin from the loss pass's histogram, histogram the middle digit of its pixels.
+// LEVEL 2: pick the middle digit's bin, histogram the last digit.
+template <int LEVEL>
+__global__ __launch_bounds__(256) void oh_refine_kernel(const float* __restrict__ lbuf, long total, long min_kept,
+                                                        unsigned* __restrict__ ctl) {
+  __shared__ unsigned h[OH_B1];
+  __shared__ unsigned s[6];
+  unsigned* cnt = ctl + OH_CNT;
+  unsigned k;
+  if (!oh_select(cnt, min_kept, k)) return;  // threshold mode: the same answer in every thread of every block
+  unsigned bin, rest, prefix;
+  if constexpr (LEVEL == 1) {
+    oh_pick<OH_B0>(ctl, k, s, bin, rest);
+    prefix = bin;
+    if (blockIdx.x == 0 && threadIdx.x == 0) { cnt[OH_BIN0] = bin; cnt[OH_NEED0] = rest; }
+  } else {
+    oh_pick<OH_B1>(ctl + OH_H1, cnt[OH_NEED0], s, bin, rest);
+    prefix = (cnt[OH_BIN0] << 10) | bin;
+    if (blockIdx.x == 0 && threadIdx.x == 0) { cnt[OH_BIN1] = bin; cnt[OH_NEED1] = rest; }
+  }
+  constexpr int SHIFT = LEVEL == 1 ? 10 : 0;  // of this level's digit; the prefix is everything above it
+  for (int i = threadIdx.x; i < OH_B1; i += blockDim.x) h[i] = 0;
+  __syncthreads();
+  for (long p = blockIdx.x * (long)blockDim.x + threadIdx.x; p < total; p += (long)gridDim.x * blockDim.x) {
+    const float l = lbuf[p];
+    const unsigned key = oh_key(l);
+    if (oh_valid(l) && (key >> (SHIFT + 10)) == prefix) atomicAdd(&h[(key >> SHIFT) & 1023u], 1u);
+  }
+  __syncthreads();
+  unsigned* out = ctl + (LEVEL == 1 ? OH_H1 : OH_H2);
+  for (int i = threadIdx.x; i < OH_B1; i += blockDim.x) {
+    const unsigned v = h[i];
+    if (v) atomicAdd(out + i, v);
+  }
+}
+
+// lambda from the last digit (+inf in threshold mode), then this block's sums of w[y] l and w[y] over K.
+__global__ __launch_bounds__(256) void oh_reduce_kernel(const float* __restrict__ lbuf,
+                                                        const long long* __restrict__ labels, long total,
+                                                        long min_kept, float tau, const float* __restrict__ cw,
+                                                        unsigned* __restrict__ ctl, float* __restrict__ part) {
+  __shared__ unsigned s[6];
+  __shared__ float red_l[4], red_d[4];
+  __shared__ unsigned kept;
+  unsigned* cnt = ctl + OH_CNT;
+  unsigned k, lbits = OH_INF;
+  if (oh_select(cnt, min_kept, k)) {
+    unsigned bin, rest;
+    oh_pick<OH_B2>(ctl + OH_H2, cnt[OH_NEED1], s, bin, rest);
+    lbits = (cnt[OH_BIN0] << 20) | (cnt[OH_BIN1] << 10) | bin;
+  }
+  const float lambda = __uint_as_float(lbits);
+  if (threadIdx.x == 0) kept = 0;
+  __syncthreads();
+  float lsum = 0.f, dsum = 0.f;
+  unsigned nk = 0;
+  for (long p = blockIdx.x * (long)blockDim.x + threadIdx.x; p < total; p += (long)gridDim.x * blockDim.x) {
+    const float l = lbuf[p];
+    if (!oh_valid(l) || !oh_keep(l, tau, lambda)) continue;
+    const float wy = cw ? cw[labels[p]] : 1.f;  // a valid pixel's label is in [0, C)
+    lsum = __builtin_fmaf(wy, l, lsum);
+    dsum += wy;
+    nk += 1u;
+  }
+  lsum = wave_sum(lsum);
+  dsum = wave_sum(dsum);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0) { red_l[wave] = lsum; red_d[wave] = dsum; }
+  if (nk) atomicAdd(&kept, nk);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    part[2 * blockIdx.x] = red_l[0] + red_l[1] + red_l[2] + red_l[3];
+    part[2 * blockIdx.x + 1] = red_d[0] + red_d[1] + red_d[2] + red_d[3];
+    if (kept) atomicAdd(cnt + OH_KEPT, kept);
+    if (blockIdx.x == 0) cnt[OH_LAMBDA] = lbits;
+  }
+}
+
+// out6 = [loss, D, #out-of-range labels, #valid, #kept, cut = min(tau, lambda)]
+__global__ void oh_finalize_kernel(const float* __restrict__ part, int nblk, float tau,
+                                   const unsigned* __restrict__ ctl, float* out) {
+  double l = 0.0, d = 0.0;
+  for (int k = threadIdx.x; k < nblk; k += 64) {
+    l += part[2 * k];
+    d += part[2 * k + 1];
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    l += __shfl_xor(l, o, 64);
+    d += __shfl_xor(d, o, 64);
+  }
+  if (threadIdx.x == 0) {
+    const unsigned* cnt = ctl + OH_CNT;
+    out[0] = cnt[OH_BAD] > 0 ? __builtin_nanf("") : (float)(l / d);  // 0/0 = nan when nothing is kept, as aten
+    out[1] = (float)d;
+    out[2] = (float)cnt[OH_BAD];
+    out[3] = (float)cnt[OH_VALID];
+    out[4] = (float)cnt[OH_KEPT];
+    out[5] = fminf(tau, __uint_as_float(cnt[OH_LAMBDA]));
+  }
+}
+
+// dhigh[p][c] = g w[y_p] (softmax(z_p)[c] - [c == y_p]) / D on K (read from the stored l_p), zeros elsewhere: the
+// weighted gradient kernel's expression, scale * (w[y] * (softmax - onehot)), so on K the rows are what
+// seg_cew_upsample_grad writes for the labels with every pixel outside K ignored.
+// NCHW (the bf16io twin): dhigh is fp32 [N][C][Ho][Wo] instead of T rows.  The low-resolution gradient then sums
+// unrounded terms, as it does behind the full-resolution logits of the model's forward; bf16 rows would put an error
+// of 2^-9 on every term, 2e-4 on the head's parameter gradients.
+template <int CP, typename T, bool NCHW>
+__global__ __launch_bounds__(256) void oh_up_grad_kernel(const T* __restrict__ low, long ld, int N, int H, int W,
+                                                         int C, const long long* __restrict__ labels, int Ho, int Wo,
+                                                         float sh, float sw, float tau, const float* __restrict__ cw,
+                                                         const float* __restrict__ lbuf,
+                                                         const unsigned* __restrict__ ctl,
+                                                         const float* __restrict__ gout,
+                                                         const float* __restrict__ stats, void* __restrict__ dout,
+                                                         long ldh) {
+  const long total = (long)N * Ho * Wo;
+  const long plane = (long)Ho * Wo;
+  const float scale = stats[2] > 0.f ? __builtin_nanf("") : gout[0] / stats[1];
+  const float lambda = __uint_as_float(ctl[OH_CNT + OH_LAMBDA]);
+  float w[CP];
+  class_weights<CP>(cw, C, w);
+  for (long p = blockIdx.x * (long)blockDim.x + threadIdx.x; p < total; p += (long)gridDim.x * blockDim.x) {
+    const float l = lbuf[p];
+    const int n = (int)(p / plane);
+    const int rem = (int)(p - (long)n * plane);
+    T* d = static_cast<T*>(dout) + p * ldh;                            // rows (!NCHW)
+    float* dn = static_cast<float*>(dout) + (long)n * C * plane + rem;  // class 0 of this pixel (NCHW)
+    if (!oh_valid(l) || !oh_keep(l, tau, lambda)) {  // out of range: scale is NaN, the loss already is
+      if constexpr (NCHW) {
+        for (int c = 0; c < C; ++c) dn[c * plane] = 0.f;
+      } else {
+#pragma unroll
+        for (int c = 0; c < CP; c += 4) st4(d + c, f32x4{0.f, 0.f, 0.f, 0.f});
+      }
+      continue;
+    }
+    const int y = (int)labels[p];
+    const int r = rem / Wo, s = rem - r * Wo;
+    float z[CP];
+    full_res_logits<CP, T>(low, ld, H, W, n, r, s, sh, sw, z);
+    float m, se, zy;
+    softmax_stats<CP>(z, C, y, m, se, zy, true);
+    const float inv = 1.f / se;
+    float wy = 0.f;
+#pragma unroll
+    for (int c = 0; c < CP; ++c) wy = c == y ? w[c] : wy;
+#pragma unroll
+    for (int c = 0; c < CP; c += 4) {
+      f32x4 o;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int cc = c + j;
+        o[j] = cc < C ? scale * (wy * __builtin_fmaf(z[cc], inv, cc == y ? -1.f : -0.f)) : 0.f;
+      }
+      if constexpr (NCHW) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          if (c + j < C) dn[(c + j) * plane] = o[j];
+      } else {
+        st4(d + c, o);
+      }
+    }
+  }
+}
+
+inline bool oh_args_ok(long ld, int C, long total, float tau, long min_kept) {
+  return !(ld & 3) && C >= 1 && C <= CMAX && ld >= C && total >= 0 && total < (1L << 31) && std::isfinite(tau) &&
+         tau >= 0.f && min_kept >= 1;
+}
+
+template <typename T, bool EVAL>
+int oh_loss_impl(const T* low, long ld, int N, int H, int W, int C, const long long* labels, int Ho, int Wo,
+                 int ignore_index, const float* cw, float tau, long min_kept, float* work, float* out6,
+                 long long* confusion, hipStream_t stream) {
+  const long total = (long)N * Ho * Wo;
+  if (!oh_args_ok(ld, C, total, tau, min_kept) || (EVAL && !confusion)) return (int)hipErrorInvalidValue;
+  const int nb = loss_blocks(total);
+  const float sh = Ho > 1 ? (float)(H - 1) / (float)(Ho - 1) : 0.f;
+  const float sw = Wo > 1 ? (float)(W - 1) / (float)(Wo - 1) : 0.f;
+  float* lbuf = work;
+  unsigned* ctl = reinterpret_cast<unsigned*>(work + total);
+  float* part = work + total + OH_CTL;
+  // every call clears its histograms and counters on the stream: a replayed tape never sees the last step's bins
+  const hipError_t e = hipMemsetAsync(ctl, 0, sizeof(unsigned) * OH_CTL, stream);
+  if (e != hipSuccess) return (int)e;
+#define SEG_OH_L(CP)                                                                                         \
+  case CP:                                                                                                   \
+    hipLaunchKernelGGL((oh_up_loss_kernel<CP, T, EVAL>), dim3(nb), dim3(256), 0, stream, low, ld, N, H, W,    \
+                       C, labels, Ho, Wo, sh, sw, ignore_index, tau, lbuf, ctl,                              \
+                       (unsigned long long*)confusion);                                                      \
+    break
+  switch ((C + 3) & ~3) {
+    SEG_OH_L(4); SEG_OH_L(8); SEG_OH_L(12); SEG_OH_L(16); SEG_OH_L(20); SEG_OH_L(24); SEG_OH_L(28); SEG_OH_L(32);
+  }
+#undef SEG_OH_L
+  hipLaunchKernelGGL(oh_refine_kernel<1>, dim3(nb), dim3(256), 0, stream, lbuf, total, min_kept, ctl);
+  hipLaunchKernelGGL(oh_refine_kernel<2>, dim3(nb), dim3(256), 0, stream, lbuf, total, min_kept, ctl);
+  hipLaunchKernelGGL(oh_reduce_kernel, dim3(nb), dim3(256), 0, stream, lbuf, labels, total, min_kept, tau, cw, ctl,
+                     part);
+  hipLaunchKernelGGL(oh_finalize_kernel, dim3(1), dim3(64), 0, stream, part, nb, tau, ctl, out6);
+  SEG_RET_LAST();
+}
+
+template <typename T, bool NCHW>
+int oh_grad_impl(const T* low, long ld, int N, int H, int W, int C, const long long* labels, int Ho, int Wo,
+                 const float* cw, float tau, const float* work, const float* grad_out, const float* stats, void* dhigh,
+                 long ldh, hipStream_t stream) {
+  const long total = (long)N * Ho * Wo;
+  if (!oh_args_ok(ld, C, total, tau, 1) || (!NCHW && ((ldh & 3) || ldh < C))) return (int)hipErrorInvalidValue;
+  const float sh = Ho > 1 ? (float)(H - 1) / (float)(Ho - 1) : 0.f;
+  const float sw = Wo > 1 ? (float)(W - 1) / (float)(Wo - 1) : 0.f;
+  const int grid = (int)std::min<long>(seg_cdiv(total, 256), 8192);
+  const unsigned* ctl = reinterpret_cast<const unsigned*>(work + total);
+#define SEG_OH_G(CP)                                                                                         \
+  case CP:                                                                                                   \
+    hipLaunchKernelGGL((oh_up_grad_kernel<CP, T, NCHW>), dim3(grid), dim3(256), 0, stream, low, ld, N, H, W, C,     \
+                       labels, Ho, Wo, sh, sw, tau, cw, work, ctl, grad_out, stats, dhigh, ldh);             \
+    break
+  switch ((C + 3) & ~3) {
+    SEG_OH_G(4); SEG_OH_G(8); SEG_OH_G(12); SEG_OH_G(16); SEG_OH_G(20); SEG_OH_G(24); SEG_OH_G(28); SEG_OH_G(32);
+  }
+#undef SEG_OH_G
+  SEG_RET_LAST();
+}
+
+}  // namespace
+
+// out6 = [loss, D, #out-of-range labels, #valid, #kept, cut]; loss_thresh is tau = -log(thresh); the first `pixels`
+// floats of `work` (>= seg_ohem_workspace_floats(N*Ho*Wo)) are the per-pixel losses, which seg_ohem_upsample_grad
+// reads back together with lambda.
+SEG_API long seg_ohem_workspace_floats(long pixels) { return pixels + OH_CTL + 2L * loss_blocks(pixels); }
+
+SEG_API int seg_ohem_upsample_loss(const float* low, long ld, int N, int H, int W, int C, const long long* labels,
+                                   int Ho, int Wo, int ignore_index, const float* class_weight, float loss_thresh,
+                                   long min_kept, float* work, float* out6, hipStream_t stream) {
+  return oh_loss_impl<float, false>(low, ld, N, H, W, C, labels, Ho, Wo, ignore_index, class_weight, loss_thresh,
+                                    min_kept, work, out6, nullptr, stream);
+}
+SEG_API int seg_ohem_upsample_loss_bf16io(const __bf16* low, long ld, int N, int H, int W, int C,
+                                          const long long* labels, int Ho, int Wo, int ignore_index,
+                                          const float* class_weight, float loss_thresh, long min_kept, float* work,
+                                          float* out6, hipStream_t stream) {
+  return oh_loss_impl<__bf16, false>(low, ld, N, H, W, C, labels, Ho, Wo, ignore_index, class_weight, loss_thresh,
+                                     min_kept, work, out6, nullptr, stream);
+}
+SEG_API int seg_ohem_upsample_eval(const float* low, long ld, int N, int H, int W, int C, const long long* labels,
+                                   int Ho, int Wo, int ignore_index, const float* class_weight, float loss_thresh,
+                                   long min_kept, float* work, float* out6, long long* confusion,
+                                   hipStream_t stream) {
+  return oh_loss_impl<float, true>(low, ld, N, H, W, C, labels, Ho, Wo, ignore_index, class_weight, loss_thresh,
+                                   min_kept, work, out6, confusion, stream);
+}
+SEG_API int seg_ohem_upsample_eval_bf16io(const __bf16* low, long ld, int N, int H, int W, int C,
+                                          const long long* labels, int Ho, int Wo, int ignore_index,
+                                          const float* class_weight, float loss_thresh, long min_kept, float* work,
+                                          float* out6, long long* confusion, hipStream_t stream) {
+  return oh_loss_impl<__bf16, true>(low, ld, N, H, W, C, labels, Ho, Wo, ignore_index, class_weight, loss_thresh,
+                                    min_kept, work, out6, confusion, stream);
+}
+SEG_API int seg_ohem_upsample_grad(const float* low, long ld, int N, int H, int W, int C, const long long* labels,
+                                   int Ho, int Wo, int ignore_index, const float* class_weight, float loss_thresh,
+                                   const float* work, const float* grad_out, const float* stats, float* dhigh,
+                                   long ldh, hipStream_t stream) {
+  return oh_grad_impl<float, false>(low, ld, N, H, W, C, labels, Ho, Wo, class_weight, loss_thresh, work, grad_out,
+                                    stats, dhigh, ldh, stream);
+}
+// The twin writes the full-resolution gradient as fp32 NCHW [N][C][Ho][Wo]: follow with
+// seg_upsample_bwd_bf16io(nchw_grad = 1, ac = 1).
+SEG_API int seg_ohem_upsample_grad_bf16io(const __bf16* low, long ld, int N, int H, int W, int C,
+                                          const long long* labels, int Ho, int Wo, int ignore_index,
+                                          const float* class_weight, float loss_thresh, const float* work,
+                                          const float* grad_out, const float* stats, float* dhigh_nchw,
+                                          hipStream_t stream) {
+  return oh_grad_impl<__bf16, true>(low, ld, N, H, W, C, labels, Ho, Wo, class_weight, loss_thresh, work, grad_out,
+                                    stats, dhigh_nchw, 0, stream);
+}

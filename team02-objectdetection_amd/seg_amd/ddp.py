@@ -344,7 +344,8 @@ class DataParallel(nn.Module):
         gradients are then averaged over the ranks -- what torch's DistributedDataParallel does with
         a weighted criterion; it is not the weighted mean over the global batch unless the shards'
         D agree.  seg_loss: seg_amd.SegLoss's ce, dice, focal_gamma, dice_smooth; its Dice sums are
-        per rank in the same way."""
+        per rank in the same way.  So is seg_amd.OhemCELoss's selection (ohem_thresh, ohem_min_kept): each
+        rank mines the hard pixels of its own shard."""
         self._pre(x)
         return self.module.forward_loss(x, target, ignore_index, weight, label_smoothing, reduction, **seg_loss)
 

@@ -45,6 +45,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes
+import math
 import os
 from typing import NamedTuple
 
@@ -1201,6 +1202,7 @@ class Run:
         self.label_smoothing = 0.0
         self.plain_loss = True  # no class weights, smoothing or "sum": the seg_ce_* kernels (else seg_cew_*)
         self.sl = None          # (ce, dice, focal_gamma, dice_smooth) of a SegLoss: the seg_sl_* kernels
+        self.ohem = None        # (tau, workspace) of an OhemCELoss: the seg_ohem_* kernels
         self.sl_table = None    # their per-class Dice gradient coefficients, written by the loss's finalize
 
     def k(self, name: str) -> str:
@@ -1651,15 +1653,26 @@ def _check_input(x: torch.Tensor):
 REDUCTIONS = {"mean": 0, "sum": 1}  # the C ABI's `reduction` (include/segamd.h: seg_cew_*)
 
 
-def loss_options(weight, label_smoothing, reduction, C, device, ce=1.0, dice=0.0, focal_gamma=0.0, dice_smooth=1.0):
+class Ohem(NamedTuple):
+    """A seg_amd.OhemCELoss's two options in loss_options' fourth slot: the seg_ohem_* kernels."""
+    thresh: float
+    min_kept: float  # an int: pixels, or a fraction of the batch's N * Ho * Wo (losses.resolve_min_kept)
+
+
+def loss_options(weight, label_smoothing, reduction, C, device, ce=1.0, dice=0.0, focal_gamma=0.0, dice_smooth=1.0,
+                 ohem_thresh=None, ohem_min_kept=None):
     """The checked (weight, label_smoothing, reduction, sl) of a fused loss over C classes on `device`; ValueError
     for what the kernels do not take.  nn.CrossEntropyLoss's options for class-index targets, reduction "none" apart,
     and seg_amd.SegLoss's: sl is None for plain cross-entropy (ce = 1, no Dice term, no focal exponent: the seg_ce_* /
-    seg_cew_* kernels, bitwise what they were), else (ce, dice, focal_gamma, dice_smooth) for the seg_sl_* kernels."""
-    from .losses import check_seg_loss_options
+    seg_cew_* kernels, bitwise what they were), else (ce, dice, focal_gamma, dice_smooth) for the seg_sl_* kernels.
+    With ohem_thresh / ohem_min_kept (a seg_amd.OhemCELoss's thresh and min_kept, both or neither) sl is an Ohem: the
+    seg_ohem_* kernels, which take class weights and nothing else."""
+    from .losses import check_ohem_options, check_seg_loss_options
     ce, dice, focal_gamma, dice_smooth = check_seg_loss_options(ce, dice, focal_gamma, label_smoothing, dice_smooth)
     sl = None if (ce == 1.0 and dice == 0.0 and focal_gamma == 0.0) else (ce, dice, focal_gamma, dice_smooth)
-    if sl is not None and reduction != "mean":
+    if ohem_thresh is not None or ohem_min_kept is not None:
+        sl = Ohem(*check_ohem_options(ohem_thresh, ohem_min_kept, label_smoothing, reduction, ce, dice, focal_gamma))
+    if sl is not None and not isinstance(sl, Ohem) and reduction != "mean":
         raise ValueError(f"a Dice or focal term (or ce != 1) is defined for reduction 'mean' only, got {reduction!r}")
     if reduction not in REDUCTIONS:
         raise ValueError(f"reduction must be 'mean' or 'sum' for the fused loss, got {reduction!r}")
@@ -1686,12 +1699,31 @@ def _loss_forward(run, t, ignore_index, confusion=None, weight=None, label_smoot
     confusion[label, argmax] (seg_ce_upsample_eval).  With class weights, label smoothing or reduction "sum"
     (loss_options) the seg_cew_* kernels run instead: stats = [loss, D, #bad labels, #valid], same first three slots.
     sl = (ce, dice, focal_gamma, dice_smooth) of a seg_amd.SegLoss: the seg_sl_* kernels, stats = [loss, D, #bad
-    labels, #valid, F, Dice] and the table of per-class Dice gradient coefficients their gradient kernel reads."""
+    labels, #valid, F, Dice] and the table of per-class Dice gradient coefficients their gradient kernel reads.
+    sl = Ohem(thresh, min_kept) of a seg_amd.OhemCELoss: the seg_ohem_* kernels, stats = [loss, D, #bad labels,
+    #valid, #kept, cut]; their workspace starts with the per-pixel losses (4 B per pixel), which the gradient
+    kernel reads back."""
     prog, lo, s = run.prog, run.prog.logits, run.stream
     N = prog.N
     Ho, Wo = prog.out_hw
     run.target, run.weight, run.label_smoothing = t, weight, label_smoothing
     run.plain_loss = sl is None and _plain_loss(weight, label_smoothing, reduction)
+    run.sl = run.ohem = None
+    if isinstance(sl, Ohem):
+        from .losses import resolve_min_kept
+        tau = -math.log(sl.thresh)  # float64 here, a float in the kernels
+        stats = run.tmp(6)
+        work = run.tmp(query("seg_ohem_workspace_floats", N * Ho * Wo))
+        args = (run.ptr(lo), lo.ld, N, lo.H, lo.W, lo.C, t.data_ptr(), Ho, Wo, ignore_index,
+                weight.data_ptr() if weight is not None else 0, tau, resolve_min_kept(sl.min_kept, N * Ho * Wo),
+                work.data_ptr(), stats.data_ptr())
+        if confusion is None:
+            run.call(run.k("seg_ohem_upsample_loss"), *args, s)
+        else:
+            run.call(run.k("seg_ohem_upsample_eval"), *args, confusion.data_ptr(), s)
+        run.ohem = (tau, work)
+        run.stats = stats
+        return stats
     run.sl = sl
     if sl is not None:
         ce, dice, gamma, smooth = sl
@@ -1736,9 +1768,30 @@ def _loss_backward(run, g, ignore_index):
     prog, lo, s = run.prog, run.prog.logits, run.stream
     N = prog.N
     Ho, Wo = prog.out_hw
+    if run.ohem is not None and run.io:
+        # the bf16io twin: the full-resolution gradient in fp32 NCHW, as behind the model's logits (bf16 rows would
+        # round every term of the low-resolution gradient's sums)
+        w = run.weight
+        tau, work = run.ohem
+        dhigh = torch.empty(max(N * lo.C * Ho * Wo, 1), device=run.device, dtype=torch.float32)
+        run.keep.append(dhigh)
+        run.call("seg_ohem_upsample_grad_bf16io", run.ptr(lo), lo.ld, N, lo.H, lo.W, lo.C, run.target.data_ptr(), Ho,
+                 Wo, ignore_index, w.data_ptr() if w is not None else 0, tau, work.data_ptr(), g.data_ptr(),
+                 run.stats.data_ptr(), dhigh.data_ptr(), s)
+        run.call(run.k("seg_upsample_bwd"), dhigh.data_ptr(), 0, 1, N, Ho, Wo, lo.C, run.gptr(lo), lo.ld, lo.H, lo.W,
+                 1, 0, s)
+        run.mark_written(lo)
+        run.backward_from_logits()
+        return
     dhigh = torch.empty(max(N * Ho * Wo * lo.ld, 1), device=run.device, dtype=run.store)
     run.keep.append(dhigh)
-    if run.sl is not None:  # the forward's options (_loss_forward)
+    if run.ohem is not None:  # the forward's options (_loss_forward)
+        w = run.weight
+        tau, work = run.ohem
+        run.call("seg_ohem_upsample_grad", run.ptr(lo), lo.ld, N, lo.H, lo.W, lo.C, run.target.data_ptr(), Ho,
+                 Wo, ignore_index, w.data_ptr() if w is not None else 0, tau, work.data_ptr(), g.data_ptr(),
+                 run.stats.data_ptr(), dhigh.data_ptr(), lo.ld, s)
+    elif run.sl is not None:  # the forward's options (_loss_forward)
         w = run.weight
         ce, dice, gamma, _ = run.sl
         run.call(run.k("seg_sl_upsample_grad"), run.ptr(lo), lo.ld, N, lo.H, lo.W, lo.C, run.target.data_ptr(), Ho,
@@ -1767,8 +1820,8 @@ class Plan:
     by the first step -- a normal program walk with every launch captured instead of
     issued -- and replayed by the following ones with the caller's input / target /
     class-weight / output / upstream-gradient pointers patched in (label smoothing, the
-    reduction and a SegLoss's four scalars are part of the plan's key; the weight VALUES are read by the kernels each
-    step; a SegLoss's stats and coefficient table are persistent buffers of the plan).  Buffers, workspaces, saved BN
+    reduction, a SegLoss's four scalars and an OhemCELoss's two are part of the plan's key; the weight VALUES are read
+    by the kernels each step; a SegLoss's stats and coefficient table are persistent buffers of the plan).  Buffers, workspaces, saved BN
     statistics and the flat parameter-gradient buffer are persistent (allocated while
     recording, ~13 GB at bs=32 256x512 fp32 -- nothing is recomputed).
 
@@ -2090,14 +2143,17 @@ def run_logits(model, x: torch.Tensor) -> torch.Tensor:
 
 def run_loss(model, x: torch.Tensor, target: torch.Tensor, ignore_index: int = IGNORE_INDEX, weight=None,
              label_smoothing: float = 0.0, reduction: str = "mean", ce: float = 1.0, dice: float = 0.0,
-             focal_gamma: float = 0.0, dice_smooth: float = 1.0) -> torch.Tensor:
-    """nn.CrossEntropyLoss(weight, ignore_index=..., reduction=..., label_smoothing=...)(model(x), target), or
-    seg_amd.SegLoss(ce, dice, focal_gamma, weight, ...)(model(x), target), with the loss fused into the final upsample
+             focal_gamma: float = 0.0, dice_smooth: float = 1.0, ohem_thresh=None,
+             ohem_min_kept=None) -> torch.Tensor:
+    """nn.CrossEntropyLoss(weight, ignore_index=..., reduction=..., label_smoothing=...)(model(x), target),
+    seg_amd.SegLoss(ce, dice, focal_gamma, weight, ...)(model(x), target) or seg_amd.OhemCELoss(ohem_thresh,
+    ohem_min_kept, weight, ...)(model(x), target), with the loss fused into the final upsample
     (csrc/loss.hip); the options are checked by loss_options (ValueError)."""
     _check_input(x)
     sync = model.__dict__.get("_segamd_sync")
     return _SegFunction.apply(model, "loss", x, target, ignore_index, sync,
-                              (weight, label_smoothing, reduction, (ce, dice, focal_gamma, dice_smooth)),
+                              (weight, label_smoothing, reduction,
+                               (ce, dice, focal_gamma, dice_smooth, ohem_thresh, ohem_min_kept)),
                               *_params_for(model, x))
 
 
@@ -2105,11 +2161,12 @@ def run_loss(model, x: torch.Tensor, target: torch.Tensor, ignore_index: int = I
 def run_metrics(model, x: torch.Tensor, target: torch.Tensor, confusion: torch.Tensor,
                 ignore_index: int = IGNORE_INDEX, weight=None, label_smoothing: float = 0.0,
                 reduction: str = "mean", ce: float = 1.0, dice: float = 0.0, focal_gamma: float = 0.0,
-                dice_smooth: float = 1.0) -> torch.Tensor:
+                dice_smooth: float = 1.0, ohem_thresh=None, ohem_min_kept=None) -> torch.Tensor:
     """Validation forward: the fused loss of run_loss, and in the same kernel
     confusion[label, argmax of the full-resolution logits] += 1 for every valid pixel
-    (csrc/loss.hip: seg_ce_upsample_eval, seg_cew_upsample_eval with loss options, or seg_sl_upsample_eval for a
-    SegLoss's Dice / focal terms -- they change the returned loss only, never the matrix).
+    (csrc/loss.hip: seg_ce_upsample_eval, seg_cew_upsample_eval with loss options, seg_sl_upsample_eval for a
+    SegLoss's Dice / focal terms or seg_ohem_upsample_eval for an OhemCELoss -- they change the returned loss only,
+    never the matrix, which counts every valid pixel).
     A forward tape only: no gradient is ever built, so
     DataParallel's buckets are not involved (sync is None).  Plans are keyed by model.training
     like the others: eval() uses the running statistics, train() the batch's."""
@@ -2127,7 +2184,8 @@ def run_metrics(model, x: torch.Tensor, target: torch.Tensor, confusion: torch.T
             or not confusion.is_contiguous()):
         raise ValueError(f"confusion must be a contiguous int64 [{C},{C}] tensor on {x.device}, got "
                          f"{tuple(confusion.shape)} {confusion.dtype} on {confusion.device}")
-    opts = loss_options(weight, label_smoothing, reduction, C, x.device, ce, dice, focal_gamma, dice_smooth)
+    opts = loss_options(weight, label_smoothing, reduction, C, x.device, ce, dice, focal_gamma, dice_smooth,
+                        ohem_thresh, ohem_min_kept)
     plan = _plan(model, prog, "metrics", ignore_index, None, False, x.device, opts)
     plan.forward(x, t, confusion, opts[0])
     return _publish_stats(model, plan.run.stats)

@@ -18,6 +18,10 @@ them.  A term whose coefficient is 0 is left out of the loss (its NaN on a batch
 the reference the fused kernels (csrc/loss.hip: seg_sl_*) are tested against.  On a seg_amd model on the GPU,
 seg_amd.train.compute_loss / validate recognise the criterion (fused_loss_options) and never build the
 full-resolution logits.
+
+OhemCELoss (below) is cross-entropy with online hard example mining: the mean over the pixels whose loss exceeds
+-log(thresh), but over no fewer than min_kept of them.  Its class docstring has the definition and the tie rule; the
+fused kernels are csrc/loss.hip's seg_ohem_*.
 """
 from __future__ import annotations
 
@@ -91,10 +95,71 @@ def seg_loss_terms(logits, target, ce=1.0, dice=0.0, focal_gamma=0.0, weight=Non
     return loss, focal, soft
 
 
+def check_ohem_options(thresh, min_kept, label_smoothing=0.0, reduction="mean", ce=1.0, dice=0.0, focal_gamma=0.0):
+    """(thresh as a float, min_kept as an int >= 1 or a float in (0, 1]); ValueError for what OhemCELoss's
+    definition excludes: label smoothing, any reduction but the mean, SegLoss's terms."""
+    if isinstance(thresh, bool) or not isinstance(thresh, (int, float)) or not 0.0 < float(thresh) < 1.0:
+        raise ValueError(f"thresh must be a probability in (0, 1), got {thresh!r}")
+    if isinstance(min_kept, bool) or not isinstance(min_kept, (int, float)):
+        raise ValueError(f"min_kept must be an int >= 1 (pixels) or a float in (0, 1] (a fraction), got {min_kept!r}")
+    if isinstance(min_kept, int):
+        if min_kept < 1:
+            raise ValueError(f"min_kept as a pixel count must be >= 1, got {min_kept!r}")
+    elif not 0.0 < min_kept <= 1.0:
+        raise ValueError(f"min_kept as a fraction of the batch's pixels must be in (0, 1], got {min_kept!r}")
+    if float(label_smoothing) != 0.0:
+        raise ValueError("online hard example mining is not defined with label smoothing")
+    if reduction != "mean":
+        raise ValueError(f"online hard example mining is defined for reduction 'mean' only, got {reduction!r}")
+    if float(ce) != 1.0 or float(dice) != 0.0 or float(focal_gamma) != 0.0:
+        raise ValueError("online hard example mining does not combine with SegLoss's ce, dice or focal_gamma")
+    return float(thresh), min_kept
+
+
+def resolve_min_kept(min_kept, pixels: int) -> int:
+    """OhemCELoss's floor as a pixel count for a batch of `pixels` = N * Ho * Wo pixels: an int as it is, a float
+    as that fraction of the batch, floored and at least 1."""
+    if isinstance(min_kept, int):
+        return min_kept
+    return max(1, int(math.floor(min_kept * pixels)))
+
+
+def ohem_loss_terms(logits, target, thresh=0.7, min_kept=1 / 16, weight=None, ignore_index=-100):
+    """(loss, kept, cut) of OhemCELoss for NCHW `logits` and class-index `target` [N, H, W], in torch ops: kept is
+    the bool mask [N, H, W] of K and cut = min(tau, lambda) as a 0-dim tensor (tau when no pixel is valid)."""
+    thresh, min_kept = check_ohem_options(thresh, min_kept)
+    C = logits.shape[1]
+    valid = target != ignore_index
+    if bool((valid & ((target < 0) | (target >= C))).any()):
+        raise IndexError("Target out of bounds: label(s) outside [0, num_classes) that are not ignore_index")
+    tau = -math.log(thresh)
+    y = torch.where(valid, target, torch.zeros_like(target))
+    l = -torch.log_softmax(logits, 1).gather(1, y.unsqueeze(1)).squeeze(1)           # [N, H, W], unweighted
+    ld = l.detach()
+    nv = int(valid.sum())
+    k = min(resolve_min_kept(min_kept, target.numel()), nv)
+    if nv:
+        lam = torch.topk(ld[valid], k, sorted=True).values[-1]                       # the k-th largest over V
+        kept = valid & ((ld > tau) | (ld >= lam))                                    # a tie group at lambda whole
+        cut = torch.clamp(lam, max=tau)
+    else:
+        kept = valid
+        cut = ld.new_tensor(tau)
+    wy = (weight.to(l.dtype)[y] if weight is not None else torch.ones_like(l)) * kept.to(l.dtype)
+    # where, not a product with the mask: a pixel outside K has gradient exactly 0
+    loss = torch.where(kept, wy * l, torch.zeros_like(l)).sum() / wy.sum()
+    return loss, kept, cut
+
+
 def criterion_loss(logits, target, ignore_index=-100, weight=None, label_smoothing=0.0, reduction="mean", ce=1.0,
-                   dice=0.0, focal_gamma=0.0, dice_smooth=1.0):
+                   dice=0.0, focal_gamma=0.0, dice_smooth=1.0, ohem_thresh=None, ohem_min_kept=None):
     """What model.forward_loss's keyword arguments describe, on full-resolution logits in torch ops: F.cross_entropy
-    for the defaults (nn.CrossEntropyLoss's options), else SegLoss's definition (reduction "mean" only)."""
+    for the defaults (nn.CrossEntropyLoss's options), else SegLoss's definition (reduction "mean" only), or
+    OhemCELoss's when ohem_thresh / ohem_min_kept are given."""
+    if ohem_thresh is not None or ohem_min_kept is not None:
+        thresh, min_kept = check_ohem_options(ohem_thresh, ohem_min_kept, label_smoothing, reduction, ce, dice,
+                                              focal_gamma)
+        return ohem_loss_terms(logits, target, thresh, min_kept, weight, ignore_index)[0]
     if float(ce) == 1.0 and float(dice) == 0.0 and float(focal_gamma) == 0.0:
         return F_.cross_entropy(logits, target, weight, ignore_index=ignore_index, reduction=reduction,
                                 label_smoothing=label_smoothing)
@@ -126,3 +191,43 @@ class SegLoss(nn.Module):
     def extra_repr(self) -> str:
         return (f"ce={self.ce}, dice={self.dice}, focal_gamma={self.focal_gamma}, ignore_index={self.ignore_index}, "
                 f"label_smoothing={self.label_smoothing}, dice_smooth={self.dice_smooth}")
+
+
+class OhemCELoss(nn.Module):
+    """Cross-entropy with online hard example mining: the mean over the pixels the model still gets wrong, but never
+    over fewer than a floor (BiSeNet's OhemCELoss(thresh, n_min) is OhemCELoss(thresh, min_kept=n_min)).
+
+    Over the valid pixels V = {p : y_p != ignore_index} of the whole batch, with l_p = logsumexp(z_p) - z_p[y_p] the
+    unweighted cross-entropy, w = weight (all ones when None), tau = -log(thresh) and k = min(min_kept, |V|):
+
+        lambda = the k-th largest l_p over V
+        K      = {p in V : l_p > tau or l_p >= lambda}
+        loss   = sum_K w[y_p] l_p / sum_K w[y_p]
+
+    min_kept: an int >= 1 is a pixel count per batch; a float in (0, 1] is that fraction of the batch's N * Ho * Wo
+    pixels, floored and at least 1 (resolved when the shape is known).  The gradient treats K as a constant, as
+    indexing does: it is exactly 0 outside K.  No valid pixel gives NaN (0/0, as aten).
+
+    Ties: every pixel whose loss equals lambda is kept, so |K| can exceed k where `loss.topk(k)` would keep an
+    arbitrary k of them; K then depends on neither the pixel order nor a kernel's thread mapping.  Without ties at
+    lambda the value is BiSeNet's (`loss[loss > tau]`, or `loss.topk(n_min)` when fewer than n_min pass).
+
+    `forward` is this definition in torch ops: the CPU path, the path of any model without `forward_loss`, and the
+    reference the fused kernels (csrc/loss.hip: seg_ohem_*) are tested against.  On a seg_amd model on the GPU,
+    seg_amd.train.compute_loss / validate recognise the criterion (fused_loss_options) and never build the
+    full-resolution logits.
+
+    Under seg_amd.ddp.DataParallel the selection is per rank (each rank mines its own shard of the batch), like
+    SegLoss's Dice sums and the BatchNorm statistics."""
+
+    def __init__(self, thresh: float = 0.7, min_kept=1 / 16, weight=None, ignore_index: int = -100):
+        super().__init__()
+        self.thresh, self.min_kept = check_ohem_options(thresh, min_kept)
+        self.ignore_index = int(ignore_index)
+        self.register_buffer("weight", weight)
+
+    def forward(self, logits: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+        return ohem_loss_terms(logits, target, self.thresh, self.min_kept, self.weight, self.ignore_index)[0]
+
+    def extra_repr(self) -> str:
+        return f"thresh={self.thresh}, min_kept={self.min_kept}, ignore_index={self.ignore_index}"

@@ -8,7 +8,8 @@ running loss, a per-epoch "Training Loss" line and a state_dict checkpoint
 MI355X differences (results are the same):
   * when `criterion` is an `nn.CrossEntropyLoss` (main.py:99; class weights,
     label smoothing and reduction "mean" / "sum" included) or a `seg_amd.SegLoss`
-    (focal exponent and soft Dice term) and the model is a
+    (focal exponent and soft Dice term) or a `seg_amd.OhemCELoss` (online hard
+    example mining) and the model is a
     seg_amd model, the loss is computed by the fused upsample+cross-entropy
     kernels (`model.forward_loss`), so the 168 MB of full-resolution logits
     per bs=32 batch are never written;
@@ -41,8 +42,14 @@ def fused_loss_options(criterion):
     None when it has to run on the full-resolution logits: anything but an nn.CrossEntropyLoss
     (a subclass with a forward of its own included), and reduction="none", whose result is a
     full-resolution tensor.  A seg_amd.SegLoss (again without a forward of its own) adds its four
-    scalars: ce, dice, focal_gamma and dice_smooth."""
-    from .losses import SegLoss
+    scalars: ce, dice, focal_gamma and dice_smooth; a seg_amd.OhemCELoss (the same rule) its two: ohem_thresh and
+    ohem_min_kept."""
+    from .losses import OhemCELoss, SegLoss
+    if isinstance(criterion, OhemCELoss):
+        if type(criterion).forward is not OhemCELoss.forward:
+            return None
+        return {"ignore_index": criterion.ignore_index, "weight": criterion.weight, "label_smoothing": 0.0,
+                "reduction": "mean", "ohem_thresh": float(criterion.thresh), "ohem_min_kept": criterion.min_kept}
     if isinstance(criterion, SegLoss):
         if type(criterion).forward is not SegLoss.forward:
             return None
@@ -216,7 +223,7 @@ def validate(model, val_loader, criterion, device, progress: bool = True, epoch:
     Returns {"loss": mean of the batch means (val_loss += loss.item(); / len(val_loader)),
     "confusion", "pixel_acc", "iou", "miou"}.  The previous train/eval mode is restored.
 
-    When `criterion` is an nn.CrossEntropyLoss or a seg_amd.SegLoss (fused_loss_options: class weights, label
+    When `criterion` is an nn.CrossEntropyLoss, a seg_amd.SegLoss or a seg_amd.OhemCELoss (fused_loss_options: class weights, label
     smoothing, reduction "mean" / "sum", Dice and focal terms included -- they change "loss" only, never the
     matrix) and the
     model has `forward_metrics`, each batch is one fused forward (loss + argmax + confusion matrix

@@ -90,7 +90,8 @@ class _SegModel(nn.Module):
 
     def forward_loss(self, x: torch.Tensor, target: torch.Tensor, ignore_index: int = -100, weight=None,
                      label_smoothing: float = 0.0, reduction: str = "mean", *, ce: float = 1.0, dice: float = 0.0,
-                     focal_gamma: float = 0.0, dice_smooth: float = 1.0) -> torch.Tensor:
+                     focal_gamma: float = 0.0, dice_smooth: float = 1.0, ohem_thresh=None,
+                     ohem_min_kept=None) -> torch.Tensor:
         """nn.CrossEntropyLoss()(self(x), target) (main.py:99, src/train.py:37) fused
         with the final upsample: the full-resolution logits are never stored.
 
@@ -101,42 +102,44 @@ class _SegModel(nn.Module):
 
         ce, dice, focal_gamma and dice_smooth are seg_amd.SegLoss's (seg_amd/losses.py has the definition): the
         loss becomes ce * F + dice * Dice with the focal exponent in F, fused in the same way (reduction "mean"
-        only).  The defaults are plain cross-entropy, on the code path it always took."""
+        only).  ohem_thresh and ohem_min_kept are seg_amd.OhemCELoss's thresh and min_kept: given (both), the loss
+        is its mean over the mined pixels, selected on the device (mean reduction, no label smoothing, none of
+        SegLoss's terms).  The defaults are plain cross-entropy, on the code path it always took."""
         if x.device.type == "cpu":
             from .losses import criterion_loss
             return criterion_loss(self(x), target, ignore_index, weight, label_smoothing, reduction, ce, dice,
-                                  focal_gamma, dice_smooth)
+                                  focal_gamma, dice_smooth, ohem_thresh, ohem_min_kept)
         from .engine import run_loss
         return run_loss(self, x, target, ignore_index, weight, label_smoothing, reduction, ce, dice, focal_gamma,
-                        dice_smooth)
+                        dice_smooth, ohem_thresh, ohem_min_kept)
 
     def forward_metrics(self, x: torch.Tensor, target: torch.Tensor, confusion: torch.Tensor,
                         ignore_index: int = -100, weight=None, label_smoothing: float = 0.0,
                         reduction: str = "mean", *, ce: float = 1.0, dice: float = 0.0, focal_gamma: float = 0.0,
-                        dice_smooth: float = 1.0) -> torch.Tensor:
+                        dice_smooth: float = 1.0, ohem_thresh=None, ohem_min_kept=None) -> torch.Tensor:
         """Validation step: returns nn.CrossEntropyLoss()(self(x), target) and adds every
         non-ignored pixel to `confusion[label, argmax(self(x))]` (int64 [C, C] on x's device, in
         place), without gradients.  On the MI355X one kernel does both from the low-resolution
         logits: the full-resolution logits are never stored.  weight, label_smoothing, reduction and
-        SegLoss's ce, dice, focal_gamma, dice_smooth (as in forward_loss) change the returned loss only, never
-        the matrix."""
+        SegLoss's ce, dice, focal_gamma, dice_smooth and OhemCELoss's ohem_thresh, ohem_min_kept (as in forward_loss)
+        change the returned loss only, never the matrix."""
         if x.device.type == "cpu":
             return _torch_metrics(self, x, target, confusion, ignore_index, weight, label_smoothing, reduction, ce,
-                                  dice, focal_gamma, dice_smooth)
+                                  dice, focal_gamma, dice_smooth, ohem_thresh, ohem_min_kept)
         from .engine import run_metrics
         return run_metrics(self, x, target, confusion, ignore_index, weight, label_smoothing, reduction, ce, dice,
-                           focal_gamma, dice_smooth)
+                           focal_gamma, dice_smooth, ohem_thresh, ohem_min_kept)
 
 
 @torch.no_grad()
 def _torch_metrics(model, x, target, confusion, ignore_index, weight=None, label_smoothing=0.0, reduction="mean",
-                   ce=1.0, dice=0.0, focal_gamma=0.0, dice_smooth=1.0):
+                   ce=1.0, dice=0.0, focal_gamma=0.0, dice_smooth=1.0, ohem_thresh=None, ohem_min_kept=None):
     """forward_metrics in torch ops (CPU tensors): F.cross_entropy raises on an out-of-range label by itself."""
     from .losses import criterion_loss
     from .metrics import add_confusion
     logits = model(x)
     loss = criterion_loss(logits, target, ignore_index, weight, label_smoothing, reduction, ce, dice, focal_gamma,
-                          dice_smooth)
+                          dice_smooth, ohem_thresh, ohem_min_kept)
     add_confusion(confusion, logits.argmax(1), target, ignore_index)
     return loss
 
