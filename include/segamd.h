@@ -410,6 +410,11 @@ int seg_add(const float* a, long lda, const float* b, long ldb, long M, int C, f
  * slice of torch.cat([skip, up]) (src/unet.py:103). */
 int seg_upsample_fwd(const float* in, long ldin, int N, int H, int W, int C,
                      float* out, long ldout, int Ho, int Wo, int ac, hipStream_t stream);
+/* Gradient of seg_upsample_fwd / seg_upsample_to_nchw, a gather without atomics.  ac = 0 / 1 as in the forward;
+ * ac = 2: align_corners=True with the tap weights of the fused losses' own upsample (csrc/loss.hip: the fraction
+ * scale * dst - floor from one fma, where ac = 1 rounds the product first as aten's float arithmetic does), i.e. the
+ * transpose of the blend the seg_kd_* kernels compute.  At 384 source rows ac = 1 puts up to 1.9e-5 on a tap weight,
+ * ac = 2 below 4.3e-6. */
 int seg_upsample_bwd(const float* dout, long ldout, int nchw_grad, int N, int Ho, int Wo, int C,
                      float* din, long ldin, int H, int W, int ac, int accumulate, hipStream_t stream);
 /* final_upsample (align_corners=True, src/unet.py:30,49): NHWC -> NCHW logits */
@@ -554,6 +559,43 @@ int seg_ohem_upsample_grad(const float* low, long ld, int N, int H, int W, int C
                            const float* class_weight, float loss_thresh, const float* work,
                            const float* grad_out, const float* stats, float* dhigh, long ldh,
                            hipStream_t stream);
+/* seg_amd.DistillLoss: pixel-wise knowledge distillation, cross-entropy plus the tempered KL divergence to a
+ * teacher's logits, fused with the same upsample (neither model's full-resolution logits are ever stored, no float
+ * atomics: two calls on the same inputs agree bitwise).  `teacher`: fp32 NHWC rows [N][Ht][Wt] with leading
+ * dimension ldt (a multiple of 4, >= C; pads ignored), upsampled to (Ho, Wo) by the same align_corners=True
+ * bilinear as `low`; (Ht, Wt) is independent of (H, W), and with Ht == Ho, Wt == Wo the taps are the pixel itself.
+ * Over the valid pixels V and the distilled pixels P (kd_ignored != 0: every pixel, else V), with z_p / u_p the
+ * student's / teacher's full-resolution logits, s = softmax(z_p / T), q = softmax(u_p / T), w = class_weight:
+ *   CE = sum_V w[y_p] (lse(z_p) - z_p[y_p]) / D,  D = sum_V w[y_p],
+ *   KD = T^2 / |P| sum_P sum_c q_c (log q_c - log s_c),   loss = ce CE + kd KD  (ce == 0: CE left out),
+ *   dloss/dz_p[c] = g [ce / D w[y_p] (softmax(z_p)_c - [c == y_p]) [p in V] + kd T / |P| (s_c - q_c) [p in P]].
+ * q and s come from one device function, so teacher rows that are bit for bit the student's rows at the same
+ * resolution give KD exactly 0 and, with ce == 0, an all-zero gradient (fp32 entry points).
+ * out6 = [loss, D, #labels outside [0, C) that are not ignore_index, #valid pixels, CE, KD]: the first four slots
+ * are seg_cew_*'s out4.  An out-of-range label makes the loss and every gradient NaN; no valid pixel gives a NaN CE
+ * (0/0, as aten) and, with kd_ignored == 0, a NaN KD.  `stats` of _grad is the out6 of _loss (D and #valid are read
+ * from it); `work` >= seg_kd_workspace_floats(N*Ho*Wo).  In the _bf16io twins `low` and `dhigh` are seg_bf16; the
+ * teacher stays fp32.  seg_kd_upsample_grad_bf16io_nchw is the gradient twin with the full-resolution gradient written
+ * as fp32 NCHW [N][C][Ho][Wo] (no `ldh`; follow with seg_upsample_bwd_bf16io(nchw_grad = 1)): the low-resolution
+ * gradient then sums unrounded terms, as behind the model's full-resolution logits -- what the engine launches, for
+ * the reason given at seg_ohem_upsample_grad_bf16io.  hipErrorInvalidValue before any launch: C outside [1, 32],
+ * ld / ldt (ldh) % 4 != 0 or < C, Ht or Wt < 1, kd <= 0, ce < 0, temperature <= 0, any of them non-finite, teacher
+ * NULL. */
+long seg_kd_workspace_floats(long pixels);
+int seg_kd_upsample_loss(const float* low, long ld, int N, int H, int W, int C,
+                         const float* teacher, long ldt, int Ht, int Wt,
+                         const long long* labels, int Ho, int Wo, int ignore_index,
+                         const float* class_weight, float ce, float kd, float temperature, int kd_ignored,
+                         float* work, float* out6, hipStream_t stream);
+int seg_kd_upsample_grad(const float* low, long ld, int N, int H, int W, int C,
+                         const float* teacher, long ldt, int Ht, int Wt,
+                         const long long* labels, int Ho, int Wo, int ignore_index,
+                         const float* class_weight, float ce, float kd, float temperature, int kd_ignored,
+                         const float* grad_out, const float* stats, float* dhigh, long ldh, hipStream_t stream);
+/* The C real channels of `rows` NHWC rows copied into caller-owned fp32 rows of leading dimension ldo (>= C, % 4;
+ * channels C..ldo-1 written as 0), one launch: a model's low-resolution logits as seg_kd_*'s `teacher`
+ * (model.forward_low_logits).  The _bf16io twin widens seg_bf16 rows. */
+int seg_low_logits_f32(const float* low, long ld, long rows, int C, float* out, long ldo, hipStream_t stream);
 
 /* ---- inference (inference.py: preprocess_image :28-46, model.eval() forward
  *      :23-25,162-163, overlay_predictions' argmax + resize :64-70) ---------- */
@@ -704,6 +746,19 @@ int seg_ohem_upsample_eval_bf16io(const seg_bf16* low, long ld, int N, int H, in
 int seg_ohem_upsample_grad_bf16io(const seg_bf16* low, long ld, int N, int H, int W, int C, const long long* labels,
     int Ho, int Wo, int ignore_index, const float* class_weight, float loss_thresh, const float* work, const float*
     grad_out, const float* stats, float* dhigh_nchw, hipStream_t stream);
+int seg_kd_upsample_loss_bf16io(const seg_bf16* low, long ld, int N, int H, int W, int C, const float* teacher, long
+    ldt, int Ht, int Wt, const long long* labels, int Ho, int Wo, int ignore_index, const float* class_weight, float ce,
+    float kd, float temperature, int kd_ignored, float* work, float* out6, hipStream_t stream);
+int seg_kd_upsample_grad_bf16io(const seg_bf16* low, long ld, int N, int H, int W, int C, const float* teacher, long
+    ldt, int Ht, int Wt, const long long* labels, int Ho, int Wo, int ignore_index, const float* class_weight, float ce,
+    float kd, float temperature, int kd_ignored, const float* grad_out, const float* stats, seg_bf16* dhigh, long ldh,
+    hipStream_t stream);
+int seg_kd_upsample_grad_bf16io_nchw(const seg_bf16* low, long ld, int N, int H, int W, int C, const float* teacher,
+    long ldt, int Ht, int Wt, const long long* labels, int Ho, int Wo, int ignore_index, const float* class_weight,
+    float ce, float kd, float temperature, int kd_ignored, const float* grad_out, const float* stats, float*
+    dhigh_nchw, hipStream_t stream);
+int seg_low_logits_f32_bf16io(const seg_bf16* low, long ld, long rows, int C, float* out, long ldo, hipStream_t
+    stream);
 int seg_upsample_fwd_bf16io(const seg_bf16* in, long ldin, int N, int H, int W, int C, seg_bf16* out, long ldout, int
     Ho, int Wo, int ac, hipStream_t stream);
 int seg_upsample_bwd_bf16io(const void* dout, long ldout, int nchw_grad, int N, int Ho, int Wo, int C, seg_bf16* din,

@@ -258,6 +258,29 @@ __device__ __forceinline__ Lin lin_index(int dst, int in, float scale, int ac) {
   return r;
 }
 
+// align_corners=True source index / weights as the fused losses form them (csrc/loss.hip: full_res_logits): the
+// fraction scale * dst - i0 comes from ONE fma, so it carries the rounding of `scale` alone.  lin_index rounds the
+// product scale * dst to fp32 first (aten's float arithmetic), which at a source coordinate near 383 puts up to
+// 1.9e-5 (half an ulp of it) on a tap weight; this form stays below 4.3e-6 there.  seg_upsample_bwd takes it as
+// ac = 2, the exact transpose of full_res_logits' blend.  Every rounding is written out.
+struct LinAC {
+  int i0, i1;
+  float l0, l1;
+};
+
+__device__ __forceinline__ LinAC lin_ac(int dst, int in, float scale) {
+#pragma clang fp contract(off)
+  const float src = scale * (float)dst;
+  int i0 = (int)floorf(src);
+  if (i0 > in - 1) i0 = in - 1;
+  LinAC r;
+  r.i0 = i0;
+  r.i1 = i0 + (i0 < in - 1 ? 1 : 0);
+  r.l1 = fminf(fmaxf(__builtin_fmaf(scale, (float)dst, -(float)i0), 0.f), 1.f);
+  r.l0 = 1.f - r.l1;
+  return r;
+}
+
 // The 2-D bilinear blend of four float4 taps -- one definition for every kernel
 // that interpolates logits, so they round identically.
 __device__ __forceinline__ f32x4 bilerp4(f32x4 v00, f32x4 v01, f32x4 v10, f32x4 v11, const Lin& lh, const Lin& lw) {

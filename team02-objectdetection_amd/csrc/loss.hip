@@ -38,22 +38,7 @@
 
 namespace {
 
-struct LinAC {
-  int i0, i1;
-  float l0, l1;
-};
-
-__device__ __forceinline__ LinAC lin_ac(int dst, int in, float scale) {
-  const float src = scale * (float)dst;
-  int i0 = (int)floorf(src);
-  if (i0 > in - 1) i0 = in - 1;
-  LinAC r;
-  r.i0 = i0;
-  r.i1 = i0 + (i0 < in - 1 ? 1 : 0);
-  r.l1 = fminf(fmaxf(__builtin_fmaf(scale, (float)dst, -(float)i0), 0.f), 1.f);
-  r.l0 = 1.f - r.l1;
-  return r;
-}
+// LinAC / lin_ac (common.h): the align_corners=True source index and tap weights of every kernel in this file.
 
 constexpr int CMAX = 32;
 
@@ -1271,4 +1256,373 @@ SEG_API int seg_ohem_upsample_grad_bf16io(const __bf16* low, long ld, int N, int
                                           hipStream_t stream) {
   return oh_grad_impl<__bf16, true>(low, ld, N, H, W, C, labels, Ho, Wo, class_weight, loss_thresh, work, grad_out,
                                     stats, dhigh_nchw, 0, stream);
+}
+
+// ---- knowledge distillation: seg_kd_* (the criterion is seg_amd.DistillLoss) ----
+// A second low-resolution tensor, the teacher's logits (fp32 NHWC rows [N][Ht][Wt], leading dimension ldt), is
+// upsampled to (Ho, Wo) by the same align_corners=True bilinear as the student's: full_res_logits on its own
+// geometry.  (Ht, Wt) is independent of (H, W); with Ht == Ho the scale is 1 and the four taps are the pixel itself.
+// Over the valid pixels V and the distilled pixels P (every pixel with kd_ignored, else V), with z_p / u_p the
+// student's / teacher's full-resolution logits, s = softmax(z_p / T), q = softmax(u_p / T), w the class weights:
+//   CE   = sum_V w[y_p] (lse(z_p) - z_p[y_p]) / D,   D = sum_V w[y_p],
+//   KD   = T^2 / |P| sum_P sum_c q_c (log q_c - log s_c),
+//   loss = ce CE + kd KD    (a term whose coefficient is 0 is left out, so its 0/0 never reaches the loss),
+//   d loss / d z_p[c] = g [ce / D w[y_p] (softmax(z_p)_c - [c = y_p]) [p in V] + kd T / |P| (s_c - q_c) [p in P]].
+// q and s come from one device function (kd_softmax) applied to u and to z: d_c = v_c / T - max, e_c = exp(d_c),
+// the sum in ascending class order.  log q_c - log s_c is (du_c - log su) - (dz_c - log sz), so teacher logits that
+// are bit for bit the student's give KD exactly 0 and s_c - q_c exactly 0.  v_c / T is v_c * (1 / T): one rounding
+// of 1 / T on the host, exact for the powers of two.
+// One pass writes five partials per block [nll, sum of w[y], #out-of-range, #valid, kd sum]; the fp64 finalize
+// forms out6 = [loss, D, #out-of-range labels, #valid, CE, KD].  The gradient kernel reads D and #valid from it.
+namespace {
+
+struct KdOpt {
+  const float* cw;  // C class weights in device memory, or NULL = all ones
+  float ce, kd;     // the two coefficients
+  float T;          // temperature
+  int all;          // kd_ignored: P is every pixel (else the valid ones)
+};
+
+inline bool kd_opt_ok(const KdOpt& o) {
+  return std::isfinite(o.ce) && std::isfinite(o.kd) && std::isfinite(o.T) && o.ce >= 0.f && o.kd > 0.f && o.T > 0.f;
+}
+
+// Teacher geometry: rows, leading dimension, size and the align_corners scales to (Ho, Wo).
+struct KdTeacher {
+  const float* rows;
+  long ld;
+  int H, W;
+  float sh, sw;
+};
+
+// softmax(v / T) over the C real classes as d_c = v_c * invT - max and e_c = exp(d_c) (0 on the padded lanes, which
+// may hold anything); returns sum_c e_c.
+template <int CP>
+__device__ __forceinline__ float kd_softmax(const float (&v)[CP], int C, float invT, float (&d)[CP], float (&e)[CP]) {
+  float m = v[0] * invT;
+#pragma unroll
+  for (int c = 1; c < CP; ++c)
+    if (c < C) m = fmaxf(m, v[c] * invT);
+  float se = 0.f;
+#pragma unroll
+  for (int c = 0; c < CP; ++c) {
+    d[c] = c < C ? v[c] * invT - m : 0.f;
+    e[c] = c < C ? expf(d[c]) : 0.f;
+    se += e[c];
+  }
+  return se;
+}
+
+template <int CP, typename T>
+__global__ __launch_bounds__(256) void kd_up_loss_kernel(const T* __restrict__ low, long ld, int N, int H, int W,
+                                                         int C, KdTeacher te, const long long* __restrict__ labels,
+                                                         int Ho, int Wo, float sh, float sw, int ignore_index,
+                                                         float* __restrict__ part, KdOpt o) {
+  constexpr int NP = 5;
+  __shared__ float red[4][NP];
+  const long total = (long)N * Ho * Wo;
+  float lsum = 0.f, cnt = 0.f, bad = 0.f, val = 0.f, ksum = 0.f;
+  float w[CP];
+  class_weights<CP>(o.cw, C, w);
+  const float invT = 1.f / o.T;
+  const bool has_ce = o.ce > 0.f;
+  for (long p = blockIdx.x * (long)blockDim.x + threadIdx.x; p < total; p += (long)gridDim.x * blockDim.x) {
+    const long long y = labels[p];
+    const bool ign = y == ignore_index;
+    const bool oob = !ign && (y < 0 || y >= C);
+    if (oob) bad += 1.f;
+    const bool valid = !ign && !oob;
+    if (!valid && !o.all) continue;
+    const int n = (int)(p / ((long)Ho * Wo));
+    const int rem = (int)(p - (long)n * Ho * Wo);
+    const int r = rem / Wo, s = rem - r * Wo;
+    float z[CP], u[CP];
+    full_res_logits<CP, T>(low, ld, H, W, n, r, s, sh, sw, z);
+    full_res_logits<CP, float>(te.rows, te.ld, te.H, te.W, n, r, s, te.sh, te.sw, u);
+    {
+      float dz[CP], ez[CP], du[CP], eu[CP];
+      const float sz = kd_softmax<CP>(z, C, invT, dz, ez);
+      const float su = kd_softmax<CP>(u, C, invT, du, eu);
+      const float lz = logf(sz), lu = logf(su), inv = 1.f / su;
+      float k = 0.f;
+#pragma unroll
+      for (int c = 0; c < CP; ++c)
+        if (c < C) k = __builtin_fmaf(eu[c] * inv, (du[c] - lu) - (dz[c] - lz), k);
+      ksum += k;
+    }
+    if (valid) {
+      val += 1.f;
+      float wy = 0.f;
+#pragma unroll
+      for (int c = 0; c < CP; ++c) wy = c == (int)y ? w[c] : wy;
+      cnt += wy;
+      if (has_ce) {
+        float m, se, zy;
+        softmax_stats<CP>(z, C, (int)y, m, se, zy, false);
+        lsum = __builtin_fmaf(wy, m + logf(se) - zy, lsum);
+      }
+    }
+  }
+  lsum = wave_sum(lsum);
+  cnt = wave_sum(cnt);
+  bad = wave_sum(bad);
+  val = wave_sum(val);
+  ksum = wave_sum(ksum);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0) {
+    red[wave][0] = lsum; red[wave][1] = cnt; red[wave][2] = bad; red[wave][3] = val; red[wave][4] = ksum;
+  }
+  __syncthreads();
+  if (threadIdx.x < NP) {
+    const int j = threadIdx.x;
+    part[NP * blockIdx.x + j] = red[0][j] + red[1][j] + red[2][j] + red[3][j];
+  }
+}
+
+// out6 = [loss, D, #out-of-range labels, #valid pixels, CE, KD].  D is the sum of w[y] over V; |P| = total
+// (kd_ignored) or #valid; 0/0 = nan as aten (CE is 0 and left out when ce == 0).
+__global__ void kd_finalize_kernel(const float* __restrict__ part, int nblk, double total, float ce, float kd,
+                                   float T, int all, float* out) {
+  double l = 0.0, c = 0.0, b = 0.0, v = 0.0, k = 0.0;
+  for (int i = threadIdx.x; i < nblk; i += 64) {
+    l += part[5 * i];
+    c += part[5 * i + 1];
+    b += part[5 * i + 2];
+    v += part[5 * i + 3];
+    k += part[5 * i + 4];
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    l += __shfl_xor(l, o, 64);
+    c += __shfl_xor(c, o, 64);
+    b += __shfl_xor(b, o, 64);
+    v += __shfl_xor(v, o, 64);
+    k += __shfl_xor(k, o, 64);
+  }
+  if (threadIdx.x == 0) {
+    const double P = all ? total : v;
+    const double CE = ce > 0.f ? l / c : 0.0;
+    const double KD = (double)T * (double)T * k / P;
+    double loss = (double)kd * KD;
+    if (ce > 0.f) loss += (double)ce * CE;
+    out[0] = b > 0.0 ? __builtin_nanf("") : (float)loss;
+    out[1] = (float)c;
+    out[2] = (float)b;
+    out[3] = (float)v;
+    out[4] = (float)CE;
+    out[5] = (float)KD;
+  }
+}
+
+// NCHW (seg_kd_upsample_grad_bf16io_nchw): dhigh is fp32 [N][C][Ho][Wo] instead of T rows, as in the seg_ohem_* twin --
+// the low-resolution gradient then sums unrounded terms, where bf16 rows put 2^-9 on every one of them.
+template <int CP, typename T, bool NCHW>
+__global__ __launch_bounds__(256) void kd_up_grad_kernel(const T* __restrict__ low, long ld, int N, int H, int W,
+                                                         int C, KdTeacher te, const long long* __restrict__ labels,
+                                                         int Ho, int Wo, float sh, float sw, int ignore_index,
+                                                         const float* __restrict__ gout,
+                                                         const float* __restrict__ stats, void* __restrict__ dout,
+                                                         long ldh, KdOpt o) {
+  const long plane = (long)Ho * Wo, total = (long)N * plane;
+  const bool poisoned = stats[2] > 0.f, has_ce = o.ce > 0.f;
+  const float nan = __builtin_nanf("");
+  const float sce = poisoned ? nan : has_ce ? gout[0] * o.ce / stats[1] : 0.f;          // g ce / D
+  const float skd = poisoned ? nan : gout[0] * o.kd * o.T / (o.all ? (float)total : stats[3]);  // g kd T / |P|
+  float w[CP];
+  class_weights<CP>(o.cw, C, w);
+  const float invT = 1.f / o.T;
+  for (long p = blockIdx.x * (long)blockDim.x + threadIdx.x; p < total; p += (long)gridDim.x * blockDim.x) {
+    const long long y = labels[p];
+    const int n = (int)(p / plane);
+    const int rem = (int)(p - (long)n * plane);
+    T* d = static_cast<T*>(dout) + p * ldh;                             // rows (!NCHW)
+    float* dn = static_cast<float*>(dout) + (long)n * C * plane + rem;  // class 0 of this pixel (NCHW)
+    const bool valid = !(y == ignore_index || y < 0 || y >= C);
+    if (!valid && !o.all) {  // out of range: the scales are NaN, the loss already is
+      if constexpr (NCHW) {
+        for (int c = 0; c < C; ++c) dn[c * plane] = 0.f;
+      } else {
+#pragma unroll
+        for (int c = 0; c < CP; c += 4) st4(d + c, f32x4{0.f, 0.f, 0.f, 0.f});
+      }
+      continue;
+    }
+    const int r = rem / Wo, s = rem - r * Wo;
+    float z[CP], u[CP];
+    full_res_logits<CP, T>(low, ld, H, W, n, r, s, sh, sw, z);
+    full_res_logits<CP, float>(te.rows, te.ld, te.H, te.W, n, r, s, te.sh, te.sw, u);
+    float dz[CP], ez[CP], du[CP], eu[CP];
+    const float sz = kd_softmax<CP>(z, C, invT, dz, ez);
+    const float su = kd_softmax<CP>(u, C, invT, du, eu);
+    const float iz = 1.f / sz, iu = 1.f / su;
+    const bool with_ce = valid && has_ce;
+    float inv = 0.f, kw = 0.f;  // 1 / sum exp(z - max), (g ce / D) w[y]
+    if (with_ce) {
+      float m, se, zy;
+      softmax_stats<CP>(z, C, (int)y, m, se, zy, true);  // z[c] = exp(z_c - max) now
+      inv = 1.f / se;
+#pragma unroll
+      for (int c = 0; c < CP; ++c) kw = c == (int)y ? w[c] : kw;
+      kw *= sce;
+    }
+#pragma unroll
+    for (int c = 0; c < CP; c += 4) {
+      f32x4 ov;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int cc = c + j;
+        const float hard = with_ce ? kw * __builtin_fmaf(z[cc], inv, cc == (int)y ? -1.f : -0.f) : 0.f;
+        ov[j] = cc < C ? __builtin_fmaf(skd, ez[cc] * iz - eu[cc] * iu, hard) : 0.f;
+      }
+      if constexpr (NCHW) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          if (c + j < C) dn[(c + j) * plane] = ov[j];
+      } else {
+        st4(d + c, ov);
+      }
+    }
+  }
+}
+
+inline bool kd_args_ok(long ld, int C, const float* teacher, long ldt, int Ht, int Wt, const KdOpt& o) {
+  return !(ld & 3) && !(ldt & 3) && C >= 1 && C <= CMAX && ld >= C && ldt >= C && Ht >= 1 && Wt >= 1 && teacher &&
+         kd_opt_ok(o);
+}
+
+inline KdTeacher kd_teacher(const float* teacher, long ldt, int Ht, int Wt, int Ho, int Wo) {
+  return KdTeacher{teacher, ldt, Ht, Wt, Ho > 1 ? (float)(Ht - 1) / (float)(Ho - 1) : 0.f,
+                   Wo > 1 ? (float)(Wt - 1) / (float)(Wo - 1) : 0.f};
+}
+
+template <typename T>
+int kd_loss_impl(const T* low, long ld, int N, int H, int W, int C, const float* teacher, long ldt, int Ht, int Wt,
+                 const long long* labels, int Ho, int Wo, int ignore_index, KdOpt o, float* work, float* out6,
+                 hipStream_t stream) {
+  if (!kd_args_ok(ld, C, teacher, ldt, Ht, Wt, o)) return (int)hipErrorInvalidValue;
+  const long total = (long)N * Ho * Wo;
+  const int nb = loss_blocks(total);
+  const float sh = Ho > 1 ? (float)(H - 1) / (float)(Ho - 1) : 0.f;
+  const float sw = Wo > 1 ? (float)(W - 1) / (float)(Wo - 1) : 0.f;
+  const KdTeacher te = kd_teacher(teacher, ldt, Ht, Wt, Ho, Wo);
+#define SEG_KD_L(CP)                                                                                         \
+  case CP:                                                                                                   \
+    hipLaunchKernelGGL((kd_up_loss_kernel<CP, T>), dim3(nb), dim3(256), 0, stream, low, ld, N, H, W, C, te,   \
+                       labels, Ho, Wo, sh, sw, ignore_index, work, o);                                       \
+    break
+  switch ((C + 3) & ~3) {
+    SEG_KD_L(4); SEG_KD_L(8); SEG_KD_L(12); SEG_KD_L(16); SEG_KD_L(20); SEG_KD_L(24); SEG_KD_L(28); SEG_KD_L(32);
+  }
+#undef SEG_KD_L
+  hipLaunchKernelGGL(kd_finalize_kernel, dim3(1), dim3(64), 0, stream, work, nb, (double)total, o.ce, o.kd, o.T,
+                     o.all, out6);
+  SEG_RET_LAST();
+}
+
+template <typename T, bool NCHW = false>
+int kd_grad_impl(const T* low, long ld, int N, int H, int W, int C, const float* teacher, long ldt, int Ht, int Wt,
+                 const long long* labels, int Ho, int Wo, int ignore_index, KdOpt o, const float* grad_out,
+                 const float* stats, void* dhigh, long ldh, hipStream_t stream) {
+  if (!kd_args_ok(ld, C, teacher, ldt, Ht, Wt, o) || (!NCHW && ((ldh & 3) || ldh < C)))
+    return (int)hipErrorInvalidValue;
+  const long total = (long)N * Ho * Wo;
+  const float sh = Ho > 1 ? (float)(H - 1) / (float)(Ho - 1) : 0.f;
+  const float sw = Wo > 1 ? (float)(W - 1) / (float)(Wo - 1) : 0.f;
+  const KdTeacher te = kd_teacher(teacher, ldt, Ht, Wt, Ho, Wo);
+  const int grid = (int)std::min<long>(seg_cdiv(total, 256), 8192);
+#define SEG_KD_G(CP)                                                                                          \
+  case CP:                                                                                                    \
+    hipLaunchKernelGGL((kd_up_grad_kernel<CP, T, NCHW>), dim3(grid), dim3(256), 0, stream, low, ld, N, H, W, C, te, \
+                       labels, Ho, Wo, sh, sw, ignore_index, grad_out, stats, dhigh, ldh, o);                 \
+    break
+  switch ((C + 3) & ~3) {
+    SEG_KD_G(4); SEG_KD_G(8); SEG_KD_G(12); SEG_KD_G(16); SEG_KD_G(20); SEG_KD_G(24); SEG_KD_G(28); SEG_KD_G(32);
+  }
+#undef SEG_KD_G
+  SEG_RET_LAST();
+}
+
+// out[row][c] = low[row][c] for c < C, 0 for C <= c < ldo: one thread per 4 channels of an output row.
+template <typename T>
+__global__ __launch_bounds__(256) void low_logits_kernel(const T* __restrict__ low, long ld, long rows, int C,
+                                                         float* __restrict__ out, long ldo) {
+  const long quads = ldo >> 2, total = rows * quads;
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const long row = i / quads;
+    const int c = (int)(i - row * quads) * 4;
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (c < C) {
+      const f32x4 x = ld4(low + row * ld + c);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) v[j] = c + j < C ? x[j] : 0.f;
+    }
+    st4(out + row * ldo + c, v);
+  }
+}
+
+template <typename T>
+int low_logits_impl(const T* low, long ld, long rows, int C, float* out, long ldo, hipStream_t stream) {
+  if ((ld & 3) || (ldo & 3) || C < 1 || ld < C || ldo < C || rows < 0 || !low || !out)
+    return (int)hipErrorInvalidValue;
+  if (rows == 0) return (int)hipSuccess;
+  const int grid = (int)std::min<long>(seg_cdiv(rows * (ldo >> 2), 256), 8192);
+  hipLaunchKernelGGL(low_logits_kernel<T>, dim3(grid), dim3(256), 0, stream, low, ld, rows, C, out, ldo);
+  SEG_RET_LAST();
+}
+
+}  // namespace
+
+// out6 = [loss, D, #out-of-range labels, #valid, CE, KD]; `work` >= seg_kd_workspace_floats(N*Ho*Wo).
+SEG_API long seg_kd_workspace_floats(long pixels) { return 5L * loss_blocks(pixels); }
+
+SEG_API int seg_kd_upsample_loss(const float* low, long ld, int N, int H, int W, int C, const float* teacher, long ldt,
+                                 int Ht, int Wt, const long long* labels, int Ho, int Wo, int ignore_index,
+                                 const float* class_weight, float ce, float kd, float temperature, int kd_ignored,
+                                 float* work, float* out6, hipStream_t stream) {
+  return kd_loss_impl(low, ld, N, H, W, C, teacher, ldt, Ht, Wt, labels, Ho, Wo, ignore_index,
+                      KdOpt{class_weight, ce, kd, temperature, kd_ignored != 0}, work, out6, stream);
+}
+SEG_API int seg_kd_upsample_loss_bf16io(const __bf16* low, long ld, int N, int H, int W, int C, const float* teacher,
+                                        long ldt, int Ht, int Wt, const long long* labels, int Ho, int Wo,
+                                        int ignore_index, const float* class_weight, float ce, float kd,
+                                        float temperature, int kd_ignored, float* work, float* out6,
+                                        hipStream_t stream) {
+  return kd_loss_impl(low, ld, N, H, W, C, teacher, ldt, Ht, Wt, labels, Ho, Wo, ignore_index,
+                      KdOpt{class_weight, ce, kd, temperature, kd_ignored != 0}, work, out6, stream);
+}
+SEG_API int seg_kd_upsample_grad(const float* low, long ld, int N, int H, int W, int C, const float* teacher, long ldt,
+                                 int Ht, int Wt, const long long* labels, int Ho, int Wo, int ignore_index,
+                                 const float* class_weight, float ce, float kd, float temperature, int kd_ignored,
+                                 const float* grad_out, const float* stats, float* dhigh, long ldh,
+                                 hipStream_t stream) {
+  return kd_grad_impl(low, ld, N, H, W, C, teacher, ldt, Ht, Wt, labels, Ho, Wo, ignore_index,
+                      KdOpt{class_weight, ce, kd, temperature, kd_ignored != 0}, grad_out, stats, dhigh, ldh, stream);
+}
+SEG_API int seg_kd_upsample_grad_bf16io(const __bf16* low, long ld, int N, int H, int W, int C, const float* teacher,
+                                        long ldt, int Ht, int Wt, const long long* labels, int Ho, int Wo,
+                                        int ignore_index, const float* class_weight, float ce, float kd,
+                                        float temperature, int kd_ignored, const float* grad_out, const float* stats,
+                                        __bf16* dhigh, long ldh, hipStream_t stream) {
+  return kd_grad_impl(low, ld, N, H, W, C, teacher, ldt, Ht, Wt, labels, Ho, Wo, ignore_index,
+                      KdOpt{class_weight, ce, kd, temperature, kd_ignored != 0}, grad_out, stats, dhigh, ldh, stream);
+}
+// seg_kd_upsample_grad_bf16io with the full-resolution gradient written as fp32 NCHW [N][C][Ho][Wo]: follow with
+// seg_upsample_bwd_bf16io(nchw_grad = 1, ac = 1).
+SEG_API int seg_kd_upsample_grad_bf16io_nchw(const __bf16* low, long ld, int N, int H, int W, int C,
+                                             const float* teacher, long ldt, int Ht, int Wt, const long long* labels,
+                                             int Ho, int Wo, int ignore_index, const float* class_weight, float ce,
+                                             float kd, float temperature, int kd_ignored, const float* grad_out,
+                                             const float* stats, float* dhigh_nchw, hipStream_t stream) {
+  return kd_grad_impl<__bf16, true>(low, ld, N, H, W, C, teacher, ldt, Ht, Wt, labels, Ho, Wo, ignore_index,
+                                    KdOpt{class_weight, ce, kd, temperature, kd_ignored != 0}, grad_out, stats,
+                                    dhigh_nchw, 0, stream);
+}
+
+// The C real channels of each NHWC row as fp32 rows the caller owns (pads 0): the teacher's low-resolution logits
+// handed to seg_kd_*.
+SEG_API int seg_low_logits_f32(const float* low, long ld, long rows, int C, float* out, long ldo, hipStream_t stream) {
+  return low_logits_impl(low, ld, rows, C, out, ldo, stream);
+}
+SEG_API int seg_low_logits_f32_bf16io(const __bf16* low, long ld, long rows, int C, float* out, long ldo,
+                                      hipStream_t stream) {
+  return low_logits_impl(low, ld, rows, C, out, ldo, stream);
 }

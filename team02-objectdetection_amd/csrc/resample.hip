@@ -19,10 +19,17 @@
 
 namespace {
 
-// Weight with which output index `dst` samples input index `i`.
+// Weight with which output index `dst` samples input index `i`.  FMA (ac = 2): the align_corners=True weights of
+// the fused losses' forward (lin_ac, common.h) in place of lin_index's.
+template <bool FMA = false>
 __device__ __forceinline__ float lin_weight(int dst, int i, int in, float scale, int ac) {
-  const Lin l = lin_index(dst, in, scale, ac);
-  return (l.i0 == i ? l.l0 : 0.f) + (l.i1 == i ? l.l1 : 0.f);
+  if constexpr (FMA) {
+    const LinAC l = lin_ac(dst, in, scale);
+    return (l.i0 == i ? l.l0 : 0.f) + (l.i1 == i ? l.l1 : 0.f);
+  } else {
+    const Lin l = lin_index(dst, in, scale, ac);
+    return (l.i0 == i ? l.l0 : 0.f) + (l.i1 == i ? l.l1 : 0.f);
+  }
 }
 
 // Output range [lo, hi] that can reference input index i.
@@ -65,7 +72,7 @@ __global__ void up_fwd_nhwc_kernel(const T* __restrict__ in, long ldin, int N, i
 // the inner loop is loads and FMAs only.
 constexpr int SMAX = 12;
 
-template <int LAYOUT, typename TI = float, typename TO = float>
+template <int LAYOUT, typename TI = float, typename TO = float, bool FMA = false>
 __global__ void up_bwd_kernel(const TI* __restrict__ dout, long ldout, int N, int Ho, int Wo, int C,
                               TO* __restrict__ din, long ldin, int H, int W, float sh, float sw, int ac,
                               int accumulate) {
@@ -93,9 +100,9 @@ __global__ void up_bwd_kernel(const TI* __restrict__ dout, long ldout, int N, in
     if (shi - slo + 1 <= SMAX) {
       float wsv[SMAX];
 #pragma unroll
-      for (int k = 0; k < SMAX; ++k) wsv[k] = slo + k <= shi ? lin_weight(slo + k, w, W, sw, ac) : 0.f;
+      for (int k = 0; k < SMAX; ++k) wsv[k] = slo + k <= shi ? lin_weight<FMA>(slo + k, w, W, sw, ac) : 0.f;
       for (int r = rlo; r <= rhi; ++r) {
-        const float wr = lin_weight(r, h, H, sh, ac);
+        const float wr = lin_weight<FMA>(r, h, H, sh, ac);
         if (wr == 0.f) continue;
 #pragma unroll
         for (int k = 0; k < SMAX; ++k)
@@ -103,10 +110,10 @@ __global__ void up_bwd_kernel(const TI* __restrict__ dout, long ldout, int N, in
       }
     } else {
       for (int r = rlo; r <= rhi; ++r) {
-        const float wr = lin_weight(r, h, H, sh, ac);
+        const float wr = lin_weight<FMA>(r, h, H, sh, ac);
         if (wr == 0.f) continue;
         for (int s = slo; s <= shi; ++s) {
-          const float ws = lin_weight(s, w, W, sw, ac);
+          const float ws = lin_weight<FMA>(s, w, W, sw, ac);
           if (ws != 0.f) add(r, s, wr * ws);
         }
       }
@@ -369,7 +376,9 @@ SEG_API int seg_upsample_fwd_bf16io(const __bf16* in, long ldin, int N, int H, i
 
 // Gradient of seg_upsample_fwd / seg_upsample_to_nchw.  nchw_grad = 1 when d_out is
 // the NCHW gradient of the model's returned logits (always fp32).  d_in is NHWC
-// (ldin >= round4(C)).
+// (ldin >= round4(C)).  ac = 2: align_corners=True with the tap weights of csrc/loss.hip's
+// full_res_logits (lin_ac) -- the transpose of the fused losses' own upsample; ac = 0 / 1 are
+// untouched (their instantiations compile none of it).
 template <typename T>
 static int upsample_bwd_impl(const void* dout, long ldout, int nchw_grad, int N, int Ho, int Wo, int C, T* din,
                              long ldin, int H, int W, int ac, int accumulate, hipStream_t stream) {
@@ -385,6 +394,15 @@ static int upsample_bwd_impl(const void* dout, long ldout, int nchw_grad, int N,
     else
       hipLaunchKernelGGL(up2_bwd_kernel<T>, dim3(grid), dim3(256), 0, stream, dn, ldout, N, C, din, ldin, H, W,
                          accumulate);
+    SEG_RET_LAST();
+  }
+  if (ac == 2) {
+    if (nchw_grad)
+      hipLaunchKernelGGL((up_bwd_kernel<1, float, T, true>), dim3(grid), dim3(256), 0, stream,
+                         static_cast<const float*>(dout), ldout, N, Ho, Wo, C, din, ldin, H, W, sh, sw, ac, accumulate);
+    else
+      hipLaunchKernelGGL((up_bwd_kernel<0, T, T, true>), dim3(grid), dim3(256), 0, stream, dn, ldout, N, Ho, Wo, C,
+                         din, ldin, H, W, sh, sw, ac, accumulate);
     SEG_RET_LAST();
   }
   if (nchw_grad)

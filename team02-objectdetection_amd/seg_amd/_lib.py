@@ -97,6 +97,12 @@ PROTOTYPES = {
     "seg_ohem_upsample_loss": (_I, [_V, _L, _I, _I, _I, _I, _V, _I, _I, _I, _V, _F, _L, _V, _V, _V]),
     "seg_ohem_upsample_eval": (_I, [_V, _L, _I, _I, _I, _I, _V, _I, _I, _I, _V, _F, _L, _V, _V, _V, _V]),
     "seg_ohem_upsample_grad": (_I, [_V, _L, _I, _I, _I, _I, _V, _I, _I, _I, _V, _F, _V, _V, _V, _V, _L, _V]),
+    "seg_kd_workspace_floats": (_L, [_L]),
+    "seg_kd_upsample_loss": (_I, [_V, _L, _I, _I, _I, _I, _V, _L, _I, _I, _V, _I, _I, _I, _V, _F, _F, _F, _I, _V, _V,
+                                  _V]),
+    "seg_kd_upsample_grad": (_I, [_V, _L, _I, _I, _I, _I, _V, _L, _I, _I, _V, _I, _I, _I, _V, _F, _F, _F, _I, _V, _V,
+                                  _V, _L, _V]),
+    "seg_low_logits_f32": (_I, [_V, _L, _L, _I, _V, _L, _V]),
     "seg_bn_fold_batch": (_I, [_V, _I, _L, _V]),
     "seg_preprocess_bgr": (_I, [_V, _I, _I, _I, _L, _V, _I, _I, _I, _F, _F, _F, _F, _F, _F, _V]),
     "seg_argmax_nearest": (_I, [_V, _L, _I, _I, _I, _I, _I, _I, _V, _I, _I, _V]),
@@ -167,12 +173,14 @@ for _n in ("seg_add", "seg_bn_stats", "seg_bn_apply", "seg_bn_backward", "seg_bn
            "seg_dw_fwd", "seg_dw_dgrad",
            "seg_dw_wgrad", "seg_ce_upsample_loss", "seg_ce_upsample_grad", "seg_ce_upsample_eval", "seg_cew_upsample_loss",
            "seg_cew_upsample_grad", "seg_cew_upsample_eval", "seg_sl_upsample_loss", "seg_sl_upsample_grad",
-           "seg_sl_upsample_eval", "seg_ohem_upsample_loss", "seg_ohem_upsample_eval",
+           "seg_sl_upsample_eval", "seg_ohem_upsample_loss", "seg_ohem_upsample_eval", "seg_kd_upsample_loss",
+           "seg_kd_upsample_grad", "seg_low_logits_f32",
            "seg_upsample_fwd",
            "seg_upsample_bwd", "seg_upsample_to_nchw", "seg_nchw_to_nhwc", "seg_maxpool2_fwd", "seg_maxpool2_bwd"):
     PROTOTYPES[_n + "_bf16io"] = PROTOTYPES[_n]
 # the twin writes fp32 NCHW: no row stride
 PROTOTYPES["seg_ohem_upsample_grad_bf16io"] = (_I, PROTOTYPES["seg_ohem_upsample_grad"][1][:-2] + [_V])
+PROTOTYPES["seg_kd_upsample_grad_bf16io_nchw"] = (_I, PROTOTYPES["seg_kd_upsample_grad"][1][:-2] + [_V])
 PROTOTYPES["seg_conv_igemm_bf16io"] = PROTOTYPES["seg_conv_igemm"]
 PROTOTYPES["seg_bn_bwd_coef_bf16io"] = PROTOTYPES["seg_bn_bwd_coef"]
 PROTOTYPES["seg_conv_igemm_bnout_bf16io"] = PROTOTYPES["seg_conv_igemm_bnout"]

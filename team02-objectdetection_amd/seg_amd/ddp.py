@@ -345,7 +345,9 @@ class DataParallel(nn.Module):
         a weighted criterion; it is not the weighted mean over the global batch unless the shards'
         D agree.  seg_loss: seg_amd.SegLoss's ce, dice, focal_gamma, dice_smooth; its Dice sums are
         per rank in the same way.  So is seg_amd.OhemCELoss's selection (ohem_thresh, ohem_min_kept): each
-        rank mines the hard pixels of its own shard."""
+        rank mines the hard pixels of its own shard.  A seg_amd.DistillLoss's kd, kd_temperature, kd_ignored and
+        teacher_logits pass through in the same way: each rank distils its own shard (the teacher is no part of the
+        wrapped module, so nothing of it is all-reduced)."""
         self._pre(x)
         return self.module.forward_loss(x, target, ignore_index, weight, label_smoothing, reduction, **seg_loss)
 

@@ -1204,6 +1204,8 @@ class Run:
         self.sl = None          # (ce, dice, focal_gamma, dice_smooth) of a SegLoss: the seg_sl_* kernels
         self.ohem = None        # (tau, workspace) of an OhemCELoss: the seg_ohem_* kernels
         self.sl_table = None    # their per-class Dice gradient coefficients, written by the loss's finalize
+        self.kd = None          # the Distill of a DistillLoss: the seg_kd_* kernels
+        self.teacher = None     # ... and the teacher's low-resolution logits (fp32 NHWC rows)
 
     def k(self, name: str) -> str:
         """C-ABI entry point of an activation kernel for this run's storage type."""
@@ -1659,20 +1661,56 @@ class Ohem(NamedTuple):
     min_kept: float  # an int: pixels, or a fraction of the batch's N * Ho * Wo (losses.resolve_min_kept)
 
 
+class Distill(NamedTuple):
+    """A seg_amd.DistillLoss's four options and the teacher tensor's geometry in loss_options' fourth slot: the
+    seg_kd_* kernels.  Ht / Wt are 0 until the teacher tensor is known (check_teacher_logits)."""
+    ce: float
+    kd: float
+    temperature: float
+    kd_ignored: bool
+    Ht: int = 0
+    Wt: int = 0
+
+
+def check_teacher_logits(teacher_logits, N, C, device):
+    """(Ht, Wt) of a teacher's low-resolution logits as the seg_kd_* kernels take them: a contiguous float32
+    [N, Ht, Wt, round4(C)] tensor on `device` (model.forward_low_logits' result); ValueError otherwise."""
+    ldt = (C + 3) & ~3
+    t = teacher_logits
+    if t is None:
+        raise ValueError("kd > 0 needs teacher_logits (the teacher's forward_low_logits(x))")
+    if (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 4 or t.device != device
+            or not t.is_contiguous() or t.shape[0] != N or t.shape[3] != ldt or t.shape[1] < 1 or t.shape[2] < 1):
+        what = f"{tuple(t.shape)} {t.dtype} on {t.device}" if isinstance(t, torch.Tensor) else type(t).__name__
+        raise ValueError(f"teacher_logits must be a contiguous float32 [{N}, Ht, Wt, {ldt}] tensor on {device} "
+                         f"(NHWC rows of {C} classes), got {what}")
+    if t.requires_grad:
+        raise ValueError("teacher_logits must not require a gradient: the teacher gets none")
+    return int(t.shape[1]), int(t.shape[2])
+
+
 def loss_options(weight, label_smoothing, reduction, C, device, ce=1.0, dice=0.0, focal_gamma=0.0, dice_smooth=1.0,
-                 ohem_thresh=None, ohem_min_kept=None):
+                 ohem_thresh=None, ohem_min_kept=None, kd=0.0, kd_temperature=1.0, kd_ignored=True):
     """The checked (weight, label_smoothing, reduction, sl) of a fused loss over C classes on `device`; ValueError
     for what the kernels do not take.  nn.CrossEntropyLoss's options for class-index targets, reduction "none" apart,
     and seg_amd.SegLoss's: sl is None for plain cross-entropy (ce = 1, no Dice term, no focal exponent: the seg_ce_* /
     seg_cew_* kernels, bitwise what they were), else (ce, dice, focal_gamma, dice_smooth) for the seg_sl_* kernels.
     With ohem_thresh / ohem_min_kept (a seg_amd.OhemCELoss's thresh and min_kept, both or neither) sl is an Ohem: the
-    seg_ohem_* kernels, which take class weights and nothing else."""
-    from .losses import check_ohem_options, check_seg_loss_options
-    ce, dice, focal_gamma, dice_smooth = check_seg_loss_options(ce, dice, focal_gamma, label_smoothing, dice_smooth)
-    sl = None if (ce == 1.0 and dice == 0.0 and focal_gamma == 0.0) else (ce, dice, focal_gamma, dice_smooth)
-    if ohem_thresh is not None or ohem_min_kept is not None:
-        sl = Ohem(*check_ohem_options(ohem_thresh, ohem_min_kept, label_smoothing, reduction, ce, dice, focal_gamma))
-    if sl is not None and not isinstance(sl, Ohem) and reduction != "mean":
+    seg_ohem_* kernels, which take class weights and nothing else.  With kd != 0 (a seg_amd.DistillLoss's kd,
+    temperature and kd_ignored) sl is a Distill: the seg_kd_* kernels, class weights and ce beside them and nothing
+    else; the teacher tensor's geometry is filled in by the caller (check_teacher_logits)."""
+    from .losses import check_distill_options, check_ohem_options, check_seg_loss_options
+    if kd != 0.0:
+        sl = Distill(*check_distill_options(ce, kd, kd_temperature, label_smoothing, reduction, dice, focal_gamma,
+                                            ohem_thresh, ohem_min_kept), bool(kd_ignored))
+    else:
+        ce, dice, focal_gamma, dice_smooth = check_seg_loss_options(ce, dice, focal_gamma, label_smoothing,
+                                                                    dice_smooth)
+        sl = None if (ce == 1.0 and dice == 0.0 and focal_gamma == 0.0) else (ce, dice, focal_gamma, dice_smooth)
+        if ohem_thresh is not None or ohem_min_kept is not None:
+            sl = Ohem(*check_ohem_options(ohem_thresh, ohem_min_kept, label_smoothing, reduction, ce, dice,
+                                          focal_gamma))
+    if sl is not None and not isinstance(sl, (Ohem, Distill)) and reduction != "mean":
         raise ValueError(f"a Dice or focal term (or ce != 1) is defined for reduction 'mean' only, got {reduction!r}")
     if reduction not in REDUCTIONS:
         raise ValueError(f"reduction must be 'mean' or 'sum' for the fused loss, got {reduction!r}")
@@ -1702,13 +1740,29 @@ def _loss_forward(run, t, ignore_index, confusion=None, weight=None, label_smoot
     labels, #valid, F, Dice] and the table of per-class Dice gradient coefficients their gradient kernel reads.
     sl = Ohem(thresh, min_kept) of a seg_amd.OhemCELoss: the seg_ohem_* kernels, stats = [loss, D, #bad labels,
     #valid, #kept, cut]; their workspace starts with the per-pixel losses (4 B per pixel), which the gradient
-    kernel reads back."""
+    kernel reads back.
+    sl = Distill(ce, kd, temperature, kd_ignored, Ht, Wt) of a seg_amd.DistillLoss: the seg_kd_* kernels over
+    run.teacher (fp32 NHWC rows [N, Ht, Wt, round4(C)]), stats = [loss, D, #bad labels, #valid, CE, KD]."""
     prog, lo, s = run.prog, run.prog.logits, run.stream
     N = prog.N
     Ho, Wo = prog.out_hw
     run.target, run.weight, run.label_smoothing = t, weight, label_smoothing
     run.plain_loss = sl is None and _plain_loss(weight, label_smoothing, reduction)
-    run.sl = run.ohem = None
+    run.sl = run.ohem = run.kd = None
+    if isinstance(sl, Distill):
+        # stats = [loss, D, #bad labels, #valid, CE, KD]; the teacher's rows (run.teacher, set by the plan) are a
+        # tape external like the class weights
+        if confusion is not None:
+            raise ValueError("validation does not distil: evaluate the criterion's hard() term")
+        te = run.teacher
+        stats = run.tmp(6)
+        work = run.tmp(query("seg_kd_workspace_floats", N * Ho * Wo))
+        run.call(run.k("seg_kd_upsample_loss"), run.ptr(lo), lo.ld, N, lo.H, lo.W, lo.C, te.data_ptr(), te.shape[3],
+                 sl.Ht, sl.Wt, t.data_ptr(), Ho, Wo, ignore_index, weight.data_ptr() if weight is not None else 0,
+                 sl.ce, sl.kd, sl.temperature, int(sl.kd_ignored), work.data_ptr(), stats.data_ptr(), s)
+        run.kd = sl
+        run.stats = stats
+        return stats
     if isinstance(sl, Ohem):
         from .losses import resolve_min_kept
         tau = -math.log(sl.thresh)  # float64 here, a float in the kernels
@@ -1783,9 +1837,30 @@ def _loss_backward(run, g, ignore_index):
         run.mark_written(lo)
         run.backward_from_logits()
         return
+    if run.kd is not None and run.io:
+        # as for an OhemCELoss: the full-resolution gradient in fp32 NCHW
+        w, te, kd = run.weight, run.teacher, run.kd
+        dhigh = torch.empty(max(N * lo.C * Ho * Wo, 1), device=run.device, dtype=torch.float32)
+        run.keep.append(dhigh)
+        run.call("seg_kd_upsample_grad_bf16io_nchw", run.ptr(lo), lo.ld, N, lo.H, lo.W, lo.C, te.data_ptr(),
+                 te.shape[3], kd.Ht, kd.Wt, run.target.data_ptr(), Ho, Wo, ignore_index,
+                 w.data_ptr() if w is not None else 0, kd.ce, kd.kd, kd.temperature, int(kd.kd_ignored),
+                 g.data_ptr(), run.stats.data_ptr(), dhigh.data_ptr(), s)
+        # ac = 2: the transpose of the kd kernels' own blend (lin_ac)
+        run.call(run.k("seg_upsample_bwd"), dhigh.data_ptr(), 0, 1, N, Ho, Wo, lo.C, run.gptr(lo), lo.ld, lo.H, lo.W,
+                 2, 0, s)
+        run.mark_written(lo)
+        run.backward_from_logits()
+        return
     dhigh = torch.empty(max(N * Ho * Wo * lo.ld, 1), device=run.device, dtype=run.store)
     run.keep.append(dhigh)
-    if run.ohem is not None:  # the forward's options (_loss_forward)
+    if run.kd is not None:  # the forward's options (_loss_forward)
+        w, te, kd = run.weight, run.teacher, run.kd
+        run.call("seg_kd_upsample_grad", run.ptr(lo), lo.ld, N, lo.H, lo.W, lo.C, te.data_ptr(), te.shape[3],
+                 kd.Ht, kd.Wt, run.target.data_ptr(), Ho, Wo, ignore_index, w.data_ptr() if w is not None else 0,
+                 kd.ce, kd.kd, kd.temperature, int(kd.kd_ignored), g.data_ptr(), run.stats.data_ptr(),
+                 dhigh.data_ptr(), lo.ld, s)
+    elif run.ohem is not None:  # the forward's options (_loss_forward)
         w = run.weight
         tau, work = run.ohem
         run.call("seg_ohem_upsample_grad", run.ptr(lo), lo.ld, N, lo.H, lo.W, lo.C, run.target.data_ptr(), Ho,
@@ -1805,8 +1880,9 @@ def _loss_backward(run, g, ignore_index):
         run.call(run.k("seg_cew_upsample_grad"), run.ptr(lo), lo.ld, N, lo.H, lo.W, lo.C, run.target.data_ptr(), Ho,
                  Wo, ignore_index, w.data_ptr() if w is not None else 0, run.label_smoothing, g.data_ptr(),
                  run.stats.data_ptr(), dhigh.data_ptr(), lo.ld, s)
+    # a DistillLoss: ac = 2, the transpose of the kd kernels' own blend (lin_ac); the other families as they were
     run.call(run.k("seg_upsample_bwd"), dhigh.data_ptr(), lo.ld, 0, N, Ho, Wo, lo.C, run.gptr(lo), lo.ld, lo.H, lo.W,
-             1, 0, s)
+             2 if run.kd is not None else 1, 0, s)
     run.mark_written(lo)
     run.backward_from_logits()
 
@@ -1820,8 +1896,9 @@ class Plan:
     by the first step -- a normal program walk with every launch captured instead of
     issued -- and replayed by the following ones with the caller's input / target /
     class-weight / output / upstream-gradient pointers patched in (label smoothing, the
-    reduction, a SegLoss's four scalars and an OhemCELoss's two are part of the plan's key; the weight VALUES are read
-    by the kernels each step; a SegLoss's stats and coefficient table are persistent buffers of the plan).  Buffers, workspaces, saved BN
+    reduction, a SegLoss's four scalars, an OhemCELoss's two and a DistillLoss's four with the teacher tensor's geometry
+    are part of the plan's key; the teacher's logits are an external like the class weights, patched per replay; the
+    weight VALUES are read by the kernels each step; a SegLoss's stats and coefficient table are persistent buffers of the plan).  Buffers, workspaces, saved BN
     statistics and the flat parameter-gradient buffer are persistent (allocated while
     recording, ~13 GB at bs=32 256x512 fp32 -- nothing is recomputed).
 
@@ -1837,6 +1914,7 @@ class Plan:
         self.run = self.fwd = self.bwd = None
         self.t = None            # the last forward's labels (loss mode)
         self.w = None            # the last forward's class weights (None: unweighted)
+        self.tl = None           # the last forward's teacher logits (a DistillLoss; None otherwise)
         self.busy = False        # a forward whose backward has not run yet
         self.timer = None        # the KernelTimer the tapes' timing is armed for
         self.fp = None           # _fingerprint(prog) the tapes were recorded against
@@ -1857,7 +1935,7 @@ class Plan:
             tape.time(TIMER.kinds, TIMER.max_replays)
             TIMER.tapes.append(tape)
 
-    def forward(self, x, t, confusion=None, weight=None):
+    def forward(self, x, t, confusion=None, weight=None, teacher=None):
         from .tape import Recorder
         main, side = self._streams()
         N, _, H, W = x.shape
@@ -1865,6 +1943,9 @@ class Plan:
         out = None
         if self.mode == "logits":
             out = torch.empty((N, self.prog.logits.C, Ho, Wo), device=x.device, dtype=torch.float32)
+        elif self.mode == "low":  # the low-resolution logits as caller-owned fp32 NHWC rows (run_low_logits)
+            lo = self.prog.logits
+            out = torch.empty((N, lo.H, lo.W, (lo.C + 3) & ~3), device=x.device, dtype=torch.float32)
         if self.fwd is None:
             rec = Recorder({side: 1, main: 0})
             rec.external("x", x.data_ptr())
@@ -1876,8 +1957,11 @@ class Plan:
                 rec.external("confusion", confusion.data_ptr())
             if weight is not None:
                 rec.external("w", weight.data_ptr())
+            if teacher is not None:
+                rec.external("tl", teacher.data_ptr())
             run = Run(self.prog, x, self.training, rec=rec, side=self.side)
             run.sync = self.sync
+            run.teacher = teacher
             if self.needs_grad:
                 ps = [p for p in self.prog.params() if p.requires_grad]
                 off = 0
@@ -1890,17 +1974,22 @@ class Plan:
             if self.mode == "logits":
                 run.call(run.k("seg_upsample_to_nchw"), run.ptr(lo), lo.ld, N, lo.H, lo.W, lo.C, out.data_ptr(), Ho,
                          Wo, 1, run.stream)
+            elif self.mode == "low":
+                run.call(run.k("seg_low_logits_f32"), run.ptr(lo), lo.ld, N * lo.H * lo.W, lo.C, out.data_ptr(),
+                         out.shape[3], run.stream)
             else:
                 _loss_forward(run, t, self.ignore_index, confusion, weight, self.label_smoothing, self.reduction,
                               self.sl)
             run.rec = None
             self.run, self.fwd = run, rec.build()
         self._arm_timer(self.fwd)
-        self.t, self.w = t, weight  # the backward tape reads the labels and the weights: keep them alive until then
+        # the backward tape reads the labels, the weights and the teacher's logits: keep them alive until then
+        self.t, self.w, self.tl = t, weight, teacher
         self.fwd.bind(x=x.data_ptr(), t=t.data_ptr() if t is not None else 0,
                       out=out.data_ptr() if out is not None else 0,
                       confusion=confusion.data_ptr() if confusion is not None else 0,
-                      w=weight.data_ptr() if weight is not None else 0)
+                      w=weight.data_ptr() if weight is not None else 0,
+                      tl=teacher.data_ptr() if teacher is not None else 0)
         self.fwd.run(main, side)
         if DEBUG_KEEP_RUN:
             global LAST_RUN
@@ -1926,6 +2015,9 @@ class Plan:
             if self.w is not None:
                 rec.external("w", self.w.data_ptr())
                 run.weight = self.w
+            if self.tl is not None:
+                rec.external("tl", self.tl.data_ptr())
+                run.teacher = self.tl
             run.rec = rec
             if self.mode == "logits":
                 prog, lo = self.prog, self.prog.logits
@@ -1940,7 +2032,8 @@ class Plan:
             self.bwd = rec.build()
         self._arm_timer(self.bwd)
         self.bwd.bind(gout=g.data_ptr(), t=self.t.data_ptr() if self.t is not None else 0,
-                      w=self.w.data_ptr() if self.w is not None else 0)
+                      w=self.w.data_ptr() if self.w is not None else 0,
+                      tl=self.tl.data_ptr() if self.tl is not None else 0)
         self.bwd.run(main, side)
         if DEBUG_KEEP_RUN:
             global LAST_RUN
@@ -2040,11 +2133,19 @@ class _SegFunction(torch.autograd.Function):
             if t.dtype != torch.int64 or tuple(t.shape) != (N, Ho, Wo):
                 raise ValueError(f"target must be int64 [{N},{Ho},{Wo}], got {tuple(t.shape)} {t.dtype}")
         needs_grad = any(ctx.needs_input_grad[7:])
+        teacher = None
         if mode == "loss":
-            weight, eps, reduction, sl = opts
+            weight, eps, reduction, sl = opts[:4]
+            tl = opts[4] if len(opts) > 4 else None  # run_loss: a DistillLoss's teacher logits
             opts = loss_options(weight, eps, reduction, prog.logits.C, x.device, *(sl or ()))
+            if isinstance(opts[3], Distill):
+                Ht, Wt = check_teacher_logits(tl, N, prog.logits.C, x.device)
+                opts = (*opts[:3], opts[3]._replace(Ht=Ht, Wt=Wt))
+                teacher = tl
+            elif tl is not None:
+                raise ValueError("teacher_logits given without kd > 0")
         plan = _plan(model, prog, mode, ignore_index, sync, needs_grad, x.device, opts)
-        out = plan.forward(x, t, weight=opts[0])
+        out = plan.forward(x, t, weight=opts[0], teacher=teacher)
         if mode == "loss":
             out = _publish_stats(model, plan.run.stats)
         else:  # an unfused criterion checks its own labels: no stale flag from an earlier fused loss
@@ -2144,17 +2245,34 @@ def run_logits(model, x: torch.Tensor) -> torch.Tensor:
 def run_loss(model, x: torch.Tensor, target: torch.Tensor, ignore_index: int = IGNORE_INDEX, weight=None,
              label_smoothing: float = 0.0, reduction: str = "mean", ce: float = 1.0, dice: float = 0.0,
              focal_gamma: float = 0.0, dice_smooth: float = 1.0, ohem_thresh=None,
-             ohem_min_kept=None) -> torch.Tensor:
+             ohem_min_kept=None, kd: float = 0.0, kd_temperature: float = 1.0, kd_ignored: bool = True,
+             teacher_logits=None) -> torch.Tensor:
     """nn.CrossEntropyLoss(weight, ignore_index=..., reduction=..., label_smoothing=...)(model(x), target),
     seg_amd.SegLoss(ce, dice, focal_gamma, weight, ...)(model(x), target) or seg_amd.OhemCELoss(ohem_thresh,
     ohem_min_kept, weight, ...)(model(x), target), with the loss fused into the final upsample
-    (csrc/loss.hip); the options are checked by loss_options (ValueError)."""
+    (csrc/loss.hip); the options are checked by loss_options (ValueError).  With kd > 0 and teacher_logits (a teacher's
+    forward_low_logits(x): float32 [N, Ht, Wt, round4(C)]) the loss is seg_amd.DistillLoss(teacher, ce, kd,
+    kd_temperature, weight, ignore_index, kd_ignored)'s, the teacher's logits upsampled inside the same kernels
+    (seg_kd_*); the tensor is read by the forward and by the backward and may be a new one every step."""
     _check_input(x)
     sync = model.__dict__.get("_segamd_sync")
-    return _SegFunction.apply(model, "loss", x, target, ignore_index, sync,
-                              (weight, label_smoothing, reduction,
-                               (ce, dice, focal_gamma, dice_smooth, ohem_thresh, ohem_min_kept)),
-                              *_params_for(model, x))
+    opts = (weight, label_smoothing, reduction, (ce, dice, focal_gamma, dice_smooth, ohem_thresh, ohem_min_kept))
+    if kd != 0.0 or teacher_logits is not None:  # the defaults keep the tuple (and the code path) they always had
+        opts = (*opts[:3], (*opts[3], kd, kd_temperature, kd_ignored), teacher_logits)
+    return _SegFunction.apply(model, "loss", x, target, ignore_index, sync, opts, *_params_for(model, x))
+
+
+@torch.no_grad()
+def run_low_logits(model, x: torch.Tensor) -> torch.Tensor:
+    """The NHWC logits in front of the final upsample as a caller-owned float32 tensor [N, Hl, Wl, round4(C)] (the
+    pad channels 0): a forward-only plan (mode "low") that ends in seg_low_logits_f32 -- no full-resolution tensor is
+    formed, in any conv math.  What a seg_amd.DistillLoss's teacher hands to run_loss as teacher_logits."""
+    _check_input(x)
+    x = x.contiguous()
+    N, _, H, W = x.shape
+    prog = get_program(model, N, H, W)
+    plan = _plan(model, prog, "low", IGNORE_INDEX, None, False, x.device)
+    return plan.forward(x, None)
 
 
 @torch.no_grad()

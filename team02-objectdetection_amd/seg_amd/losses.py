@@ -22,6 +22,10 @@ full-resolution logits.
 OhemCELoss (below) is cross-entropy with online hard example mining: the mean over the pixels whose loss exceeds
 -log(thresh), but over no fewer than min_kept of them.  Its class docstring has the definition and the tie rule; the
 fused kernels are csrc/loss.hip's seg_ohem_*.
+
+DistillLoss (below) is pixel-wise knowledge distillation: cross-entropy plus T^2 KL(softmax(teacher / T) ||
+softmax(student / T)) against a second model's logits.  Its class docstring has the definition; the fused kernels are
+csrc/loss.hip's seg_kd_*.
 """
 from __future__ import annotations
 
@@ -151,6 +155,59 @@ def ohem_loss_terms(logits, target, thresh=0.7, min_kept=1 / 16, weight=None, ig
     return loss, kept, cut
 
 
+def check_distill_options(ce, kd, temperature, label_smoothing=0.0, reduction="mean", dice=0.0, focal_gamma=0.0,
+                          ohem_thresh=None, ohem_min_kept=None):
+    """(ce, kd, temperature) as floats; ValueError for what DistillLoss's definition excludes: kd <= 0, ce < 0,
+    temperature <= 0, a non-finite one, label smoothing, any reduction but the mean, SegLoss's Dice / focal terms
+    and online hard example mining."""
+    ce, kd, T = float(ce), float(kd), float(temperature)
+    if not (math.isfinite(kd) and kd > 0.0):
+        raise ValueError(f"kd must be a finite number > 0, got {kd!r}")
+    if not (math.isfinite(ce) and ce >= 0.0):
+        raise ValueError(f"ce must be a finite number >= 0, got {ce!r}")
+    if not (math.isfinite(T) and T > 0.0):
+        raise ValueError(f"temperature must be a finite number > 0, got {T!r}")
+    if float(label_smoothing) != 0.0:
+        raise ValueError("distillation is not defined with label smoothing")
+    if reduction != "mean":
+        raise ValueError(f"distillation is defined for reduction 'mean' only, got {reduction!r}")
+    if float(dice) != 0.0 or float(focal_gamma) != 0.0:
+        raise ValueError("distillation does not combine with SegLoss's dice or focal_gamma")
+    if ohem_thresh is not None or ohem_min_kept is not None:
+        raise ValueError("distillation does not combine with online hard example mining")
+    return ce, kd, T
+
+
+def distill_loss_terms(logits, teacher_logits, target, ce=1.0, kd=1.0, temperature=2.0, weight=None,
+                       ignore_index=-100, kd_ignored=True):
+    """(loss, CE, KD) of DistillLoss for NCHW `logits` and `teacher_logits` [N, C, Ho, Wo] and class-index `target`
+    [N, Ho, Wo], in torch ops; differentiable in `logits` only.  CE is None when ce == 0 (the term is left out)."""
+    ce, kd, T = check_distill_options(ce, kd, temperature)
+    if teacher_logits.shape != logits.shape:
+        raise ValueError(f"teacher_logits must have the logits' shape {tuple(logits.shape)}, got "
+                         f"{tuple(teacher_logits.shape)}")
+    C = logits.shape[1]
+    valid = target != ignore_index
+    if bool((valid & ((target < 0) | (target >= C))).any()):
+        raise IndexError("Target out of bounds: label(s) outside [0, num_classes) that are not ignore_index")
+    if weight is not None:
+        weight = weight.to(logits.dtype)
+    hard = None
+    if ce > 0.0:
+        hard = F_.cross_entropy(logits, target, weight, ignore_index=ignore_index, reduction="mean")
+    u = teacher_logits.detach().to(logits.dtype)
+    logq = torch.log_softmax(u / T, 1)
+    logs = torch.log_softmax(logits / T, 1)
+    kl = (logq.exp() * (logq - logs)).sum(1)                                         # [N, Ho, Wo]
+    if kd_ignored:
+        soft = kl.sum() * (T * T) / kl.numel()
+    else:
+        # where, not a product with the mask: a pixel outside P has gradient exactly 0
+        soft = torch.where(valid, kl, torch.zeros_like(kl)).sum() * (T * T) / valid.sum()
+    loss = kd * soft if hard is None else ce * hard + kd * soft
+    return loss, hard, soft
+
+
 def criterion_loss(logits, target, ignore_index=-100, weight=None, label_smoothing=0.0, reduction="mean", ce=1.0,
                    dice=0.0, focal_gamma=0.0, dice_smooth=1.0, ohem_thresh=None, ohem_min_kept=None):
     """What model.forward_loss's keyword arguments describe, on full-resolution logits in torch ops: F.cross_entropy
@@ -231,3 +288,69 @@ class OhemCELoss(nn.Module):
 
     def extra_repr(self) -> str:
         return f"thresh={self.thresh}, min_kept={self.min_kept}, ignore_index={self.ignore_index}"
+
+
+class DistillLoss(nn.Module):
+    """Pixel-wise knowledge distillation: hard-label cross-entropy plus the tempered KL divergence to a teacher.
+
+    Over the valid pixels V = {p : y_p != ignore_index} and the distilled pixels P (every pixel with kd_ignored=True
+    -- the teacher also supervises unlabelled regions -- else V), with z_p the student's logits, u_p the teacher's,
+    T the temperature, s = softmax(z_p / T), q = softmax(u_p / T) and w = weight (all ones when None):
+
+        CE   = sum_V w[y_p] (logsumexp(z_p) - z_p[y_p]) / sum_V w[y_p]     (nn.CrossEntropyLoss(weight, ignore_index))
+        KD   = T^2 / |P| sum_P sum_c q_c (log q_c - log s_c)
+        loss = ce CE + kd KD
+
+    A term whose coefficient is 0 is left out, so ce = 0 on a batch without valid pixels is not NaN.  The teacher
+    gets no gradient.  Label smoothing, reductions other than the mean, Dice / focal terms and online hard example
+    mining are not combined with distillation (ValueError).
+
+    `teacher` is held but NOT registered as a submodule: the criterion's parameters(), state_dict() and .to() do not
+    include it, so no checkpoint of the student contains the teacher's weights; move the teacher to the device
+    yourself.  The constructor puts it in eval mode and clears requires_grad on its parameters; using the criterion
+    while the teacher is in training mode raises.
+
+    `forward(logits, target, teacher_logits)` is the definition in torch ops on full-resolution logits: the CPU
+    path, the path of any model without `forward_loss`, and the reference the fused kernels (csrc/loss.hip:
+    seg_kd_*) are tested against.  On seg_amd models on the GPU, seg_amd.train.compute_loss recognises the criterion
+    (fused_loss_options), asks the teacher for its low-resolution logits (forward_low_logits) and never builds
+    either model's full-resolution logits.  validate() evaluates hard(): validation does not distil.
+
+    Under seg_amd.ddp.DataParallel every rank distils its own shard; the gradients are averaged."""
+
+    def __init__(self, teacher: nn.Module, ce: float = 1.0, kd: float = 1.0, temperature: float = 2.0, weight=None,
+                 ignore_index: int = -100, kd_ignored: bool = True):
+        super().__init__()
+        self.ce, self.kd, self.temperature = check_distill_options(ce, kd, temperature)
+        self.ignore_index = int(ignore_index)
+        self.kd_ignored = bool(kd_ignored)
+        self.register_buffer("weight", weight)
+        if not isinstance(teacher, nn.Module):
+            raise TypeError(f"teacher must be an nn.Module, got {type(teacher).__name__}")
+        teacher.eval()
+        teacher.requires_grad_(False)
+        object.__setattr__(self, "teacher", teacher)  # not a submodule: see the class docstring
+
+    def _check_teacher(self):
+        if self.teacher.training:
+            raise RuntimeError("DistillLoss: the teacher is in training mode; call teacher.eval() (its BatchNorm "
+                               "statistics must not follow the student's batches)")
+
+    def forward(self, logits: torch.Tensor, target: torch.Tensor, teacher_logits: torch.Tensor) -> torch.Tensor:
+        self._check_teacher()
+        return distill_loss_terms(logits, teacher_logits, target, self.ce, self.kd, self.temperature, self.weight,
+                                  self.ignore_index, self.kd_ignored)[0]
+
+    def teacher_logits(self, x: torch.Tensor) -> torch.Tensor:
+        """The teacher's full-resolution logits for the batch `x`, without gradients."""
+        self._check_teacher()
+        with torch.no_grad():
+            return self.teacher(x)
+
+    def hard(self) -> nn.CrossEntropyLoss:
+        """The criterion's cross-entropy term as a criterion of its own (what validate() evaluates)."""
+        return nn.CrossEntropyLoss(self.weight, ignore_index=self.ignore_index)
+
+    def extra_repr(self) -> str:
+        return (f"teacher={type(self.teacher).__name__}, ce={self.ce}, kd={self.kd}, "
+                f"temperature={self.temperature}, ignore_index={self.ignore_index}, kd_ignored={self.kd_ignored}")

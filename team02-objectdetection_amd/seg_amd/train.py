@@ -9,7 +9,8 @@ MI355X differences (results are the same):
   * when `criterion` is an `nn.CrossEntropyLoss` (main.py:99; class weights,
     label smoothing and reduction "mean" / "sum" included) or a `seg_amd.SegLoss`
     (focal exponent and soft Dice term) or a `seg_amd.OhemCELoss` (online hard
-    example mining) and the model is a
+    example mining) or a `seg_amd.DistillLoss` (knowledge distillation from a
+    seg_amd teacher, whose logits are upsampled inside the same kernels) and the model is a
     seg_amd model, the loss is computed by the fused upsample+cross-entropy
     kernels (`model.forward_loss`), so the 168 MB of full-resolution logits
     per bs=32 batch are never written;
@@ -43,8 +44,15 @@ def fused_loss_options(criterion):
     (a subclass with a forward of its own included), and reduction="none", whose result is a
     full-resolution tensor.  A seg_amd.SegLoss (again without a forward of its own) adds its four
     scalars: ce, dice, focal_gamma and dice_smooth; a seg_amd.OhemCELoss (the same rule) its two: ohem_thresh and
-    ohem_min_kept."""
-    from .losses import OhemCELoss, SegLoss
+    ohem_min_kept; a seg_amd.DistillLoss (the same rule) ce, kd, kd_temperature and kd_ignored -- the teacher's
+    logits are compute_loss's to add."""
+    from .losses import DistillLoss, OhemCELoss, SegLoss
+    if isinstance(criterion, DistillLoss):
+        if type(criterion).forward is not DistillLoss.forward:
+            return None
+        return {"ignore_index": criterion.ignore_index, "weight": criterion.weight, "label_smoothing": 0.0,
+                "reduction": "mean", "ce": float(criterion.ce), "kd": float(criterion.kd),
+                "kd_temperature": float(criterion.temperature), "kd_ignored": bool(criterion.kd_ignored)}
     if isinstance(criterion, OhemCELoss):
         if type(criterion).forward is not OhemCELoss.forward:
             return None
@@ -156,9 +164,20 @@ def _step_and_loss(model, inputs, optimizer, loss, max_grad_norm=None, ema=None)
 
 
 def compute_loss(model, criterion, inputs, targets):
-    """criterion(model(inputs), targets), fused when the pair allows it."""
+    """criterion(model(inputs), targets), fused when the pair allows it.  A seg_amd.DistillLoss is fused when both
+    models are seg_amd models on the GPU: the teacher's forward_low_logits(inputs) goes to the student's forward_loss
+    as teacher_logits and neither model's full-resolution logits are formed; otherwise it is
+    criterion(model(inputs), targets, criterion.teacher_logits(inputs))."""
+    from .losses import DistillLoss
     core = getattr(model, "module", model)
     opts = fused_loss_options(criterion) if hasattr(core, "forward_loss") else None
+    if isinstance(criterion, DistillLoss):
+        teacher = getattr(criterion.teacher, "module", criterion.teacher)
+        if opts is not None and inputs.is_cuda and hasattr(teacher, "forward_low_logits"):
+            if teacher.training:
+                raise RuntimeError("DistillLoss: the teacher is in training mode; call teacher.eval()")
+            return model.forward_loss(inputs, targets, teacher_logits=teacher.forward_low_logits(inputs), **opts)
+        return criterion(model(inputs), targets, criterion.teacher_logits(inputs))
     if opts is not None:
         return model.forward_loss(inputs, targets, **opts)
     return criterion(model(inputs), targets)
@@ -232,8 +251,15 @@ def validate(model, val_loader, criterion, device, progress: bool = True, epoch:
     once, at the end of the pass -- so the bar shows no per-batch loss.  An out-of-range label
     raises IndexError there.  Under torch.distributed every rank evaluates its own shard; the
     matrices and [sum of batch losses, #batches, #bad labels] are summed with one all-reduce each
-    (on the wrapper's process group when the model has one) and every rank returns the same dict."""
+    (on the wrapper's process group when the model has one) and every rank returns the same dict.
+
+    A seg_amd.DistillLoss is evaluated as its hard() term, nn.CrossEntropyLoss(weight, ignore_index): the student's
+    validation loss is a hard-label quantity (train_model's best_checkpoint compares it) and no teacher forward
+    runs."""
+    from .losses import DistillLoss
     from .metrics import add_confusion, summarize
+    if isinstance(criterion, DistillLoss):
+        criterion = criterion.hard()  # validation does not distil: hard-label loss and mIoU, no teacher forward
     core = getattr(model, "module", model)
     ignore_index = getattr(criterion, "ignore_index", -100)
     opts = fused_loss_options(criterion) if hasattr(core, "forward_metrics") else None
@@ -311,6 +337,11 @@ def train_model(model, train_loader, criterion, optimizer, device, epochs=10,
     rank keeps its own EMA (averaged gradients and broadcast BatchNorm statistics keep them equal without a
     collective) and rank 0 writes the files.  One line at the start says which weights validation uses."""
     from .freeze import freeze as _freeze, unfreeze as _unfreeze
+    from .losses import DistillLoss
+    if isinstance(criterion, DistillLoss) and _is_rank0():
+        print(f"Distils from a {type(criterion.teacher).__name__} (ce {criterion.ce:g}, kd {criterion.kd:g}, "
+              f"temperature {criterion.temperature:g}, unlabelled pixels "
+              f"{'distilled' if criterion.kd_ignored else 'left out'}); validation uses the hard-label loss")
     if freeze is not None:
         if isinstance(freeze, (str, nn.Module)):
             freeze = [freeze]

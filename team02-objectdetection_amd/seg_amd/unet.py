@@ -91,7 +91,8 @@ class _SegModel(nn.Module):
     def forward_loss(self, x: torch.Tensor, target: torch.Tensor, ignore_index: int = -100, weight=None,
                      label_smoothing: float = 0.0, reduction: str = "mean", *, ce: float = 1.0, dice: float = 0.0,
                      focal_gamma: float = 0.0, dice_smooth: float = 1.0, ohem_thresh=None,
-                     ohem_min_kept=None) -> torch.Tensor:
+                     ohem_min_kept=None, kd: float = 0.0, kd_temperature: float = 1.0, kd_ignored: bool = True,
+                     teacher_logits=None) -> torch.Tensor:
         """nn.CrossEntropyLoss()(self(x), target) (main.py:99, src/train.py:37) fused
         with the final upsample: the full-resolution logits are never stored.
 
@@ -104,14 +105,28 @@ class _SegModel(nn.Module):
         loss becomes ce * F + dice * Dice with the focal exponent in F, fused in the same way (reduction "mean"
         only).  ohem_thresh and ohem_min_kept are seg_amd.OhemCELoss's thresh and min_kept: given (both), the loss
         is its mean over the mined pixels, selected on the device (mean reduction, no label smoothing, none of
-        SegLoss's terms).  The defaults are plain cross-entropy, on the code path it always took."""
+        SegLoss's terms).  kd, kd_temperature and kd_ignored are seg_amd.DistillLoss's kd, temperature and kd_ignored
+        and teacher_logits its teacher's forward_low_logits(x): given kd > 0 (with the tensor), the loss is ce * CE +
+        kd * KD against the teacher, whose logits are upsampled inside the loss kernels like the student's (mean
+        reduction, class weights, nothing else; GPU tensors only -- on the CPU use the criterion itself).  The
+        defaults are plain cross-entropy, on the code path it always took."""
         if x.device.type == "cpu":
+            if kd != 0.0 or teacher_logits is not None:
+                raise RuntimeError("forward_loss with kd > 0 runs on the MI355X HIP path only; on CPU tensors "
+                                   "evaluate the DistillLoss on the models' logits (seg_amd.train.compute_loss does)")
             from .losses import criterion_loss
             return criterion_loss(self(x), target, ignore_index, weight, label_smoothing, reduction, ce, dice,
                                   focal_gamma, dice_smooth, ohem_thresh, ohem_min_kept)
         from .engine import run_loss
         return run_loss(self, x, target, ignore_index, weight, label_smoothing, reduction, ce, dice, focal_gamma,
-                        dice_smooth, ohem_thresh, ohem_min_kept)
+                        dice_smooth, ohem_thresh, ohem_min_kept, kd, kd_temperature, kd_ignored, teacher_logits)
+
+    def forward_low_logits(self, x: torch.Tensor) -> torch.Tensor:
+        """The logits in front of the final upsample, without gradients: a float32 tensor [N, Hl, Wl, round4(C)] of
+        NHWC rows (pad channels 0) that the caller owns.  No full-resolution tensor is formed.  It is what a
+        seg_amd.DistillLoss's teacher feeds the student's forward_loss as teacher_logits; GPU tensors only."""
+        from .engine import run_low_logits
+        return run_low_logits(self, x)
 
     def forward_metrics(self, x: torch.Tensor, target: torch.Tensor, confusion: torch.Tensor,
                         ignore_index: int = -100, weight=None, label_smoothing: float = 0.0,
