@@ -331,6 +331,13 @@ int seg_dw_fwd_bias_act(const float* in, long ldin, int N, int H, int W, int C, 
 int seg_dw_dgrad(const float* dy, long lddy, int N, int Ho, int Wo, int C, const float* wk,
                  float* dx, long lddx, int H, int W, int stride, int accumulate, hipStream_t stream);
 long seg_dw_wgrad_blocks(int N, int Ho, int Wo, int C);
+/* The launch geometry of seg_dw_wgrad for this output shape, from the code the launch itself uses: out7 = {TC
+ * channel-group lanes per block, gy channel chunks, RG row groups, strips per block, row blocks (==
+ * seg_dw_wgrad_blocks), the weight gradient's strip width, the forward / data gradient's strip width}.  Strips are
+ * out7[5] consecutive output pixels of one output row in (n, ho, strip) order; row block b sums the strips
+ * [b * out7[3], min(nstrips, (b + 1) * out7[3])) into part[b][tap][C], and every launch writes all blocks * 9 * C
+ * floats.  A host function; hipErrorInvalidValue, nothing written, for C % 4, non-positive sizes or a null out7. */
+int seg_dw_wgrad_geometry(int N, int Ho, int Wo, int C, int* out7);
 int seg_dw_wgrad(const float* dy, long lddy, const float* x, long ldx, int N, int H, int W, int C,
                  const float* in_scale, const float* in_shift, int in_act,
                  int Ho, int Wo, int stride, float* part, hipStream_t stream);

@@ -16,6 +16,17 @@
 // in-image pixels only), as in the reference where padding follows the ReLU6.
 //
 // Weights are packed tap-major wk[9][C] (seg_pack_dw_weight).
+//
+// The contract tests/test_gpu_dw_matrix.py holds the kernels to (the numbers from seg_dw_wgrad_geometry):
+//  * Forward and data gradient run one work item per (strip of out[6] = SEG_DW_TW consecutive output pixels of one
+//    output row, float4 channel group), the channel group fastest, 256 items per block; an item stores only the
+//    in-row pixels of its strip and only its 4 channels of `ldout`-strided rows.
+//  * The weight gradient's strips are out[5] = SEG_DW_TWW consecutive output pixels of one output row, numbered in
+//    (n, ho, strip) order: nstrips = N * Ho * ceil(Wo / out[5]).  Row block b sums the strips
+//    [b * spb, min(nstrips, (b + 1) * spb)), spb = out[3]; there are out[4] = ceil(nstrips / spb) row blocks and
+//    none of them is empty.  The launch is out[4] * out[1] blocks: channel chunk y of out[0] float4 groups.
+//  * The partial layout is part[b][tap][C], tap = 3 ky + kx.  Every one of the blocks * 9 * C floats is written by
+//    every launch (no zero fill is needed), in a fixed order: the same call gives the same bits.
 #include "common.h"
 
 namespace {
@@ -327,25 +338,27 @@ __global__ __launch_bounds__(256) void dw_wgrad_kernel(const T* __restrict__ dy,
 
 int item_grid(long total) { return (int)seg_cdiv(total, 256); }
 
-// Channel-group tiling of the weight-gradient block: TC lanes of channel
-// groups (<= 64, balanced over the chunks), RG = 256 / TC row groups.
-void wgrad_tiling(int C, int* TC, int* gy) {
-  const int CG = C >> 2;
-  const int chunks = (CG + 63) / 64;
-  *TC = (CG + chunks - 1) / chunks;
-  *gy = chunks;
-}
+// The launch geometry of the weight gradient -- the one place it is computed: seg_dw_wgrad's launch,
+// seg_dw_wgrad_blocks and seg_dw_wgrad_geometry all read it from here.  TC lanes of channel groups per block
+// (<= 64, balanced over the gy channel chunks), RG = 256 / TC row groups, `spb` strips per block, gx row blocks.
+struct WgradGeo {
+  int TC, gy, RG, spb;
+  long gx;
+};
 
-void wgrad_grid(int N, int Ho, int Wo, int C, long* gx, int* spb) {
-  int TC, gy;
-  wgrad_tiling(C, &TC, &gy);
-  const int RG = 256 / TC;
+WgradGeo wgrad_geo(int N, int Ho, int Wo, int C) {
+  WgradGeo g;
+  const int CG = C >> 2;
+  g.gy = (CG + 63) / 64;
+  g.TC = (CG + g.gy - 1) / g.gy;
+  g.RG = 256 / g.TC;
   const long nstrips = (long)N * Ho * ((Wo + TWW - 1) / TWW);
-  long bx = std::max<long>(1, SEG_DW_WG_BLOCKS / gy);                              // blocks in all
-  bx = std::min<long>(bx, std::max<long>(1, nstrips / ((long)SEG_DW_WG_MINSTRIPS * RG)));  // strips per thread
-  long per = (nstrips + bx - 1) / bx;
-  *spb = (int)per;
-  *gx = (nstrips + per - 1) / per;
+  long bx = std::max<long>(1, SEG_DW_WG_BLOCKS / g.gy);                                      // blocks in all
+  bx = std::min<long>(bx, std::max<long>(1, nstrips / ((long)SEG_DW_WG_MINSTRIPS * g.RG)));  // strips per thread
+  const long per = (nstrips + bx - 1) / bx;
+  g.spb = (int)per;
+  g.gx = (nstrips + per - 1) / per;
+  return g;
 }
 
 }  // namespace
@@ -432,10 +445,15 @@ SEG_API int seg_dw_dgrad_bf16io(const __bf16* dy, long lddy, int N, int Ho, int 
 }
 
 SEG_API long seg_dw_wgrad_blocks(int N, int Ho, int Wo, int C) {
-  long gx;
-  int spb;
-  wgrad_grid(N, Ho, Wo, C, &gx, &spb);
-  return gx;
+  return wgrad_geo(N, Ho, Wo, C).gx;
+}
+
+SEG_API int seg_dw_wgrad_geometry(int N, int Ho, int Wo, int C, int* out7) {
+  if (!out7 || N <= 0 || Ho <= 0 || Wo <= 0 || C <= 0 || (C & 3)) return (int)hipErrorInvalidValue;
+  const WgradGeo g = wgrad_geo(N, Ho, Wo, C);
+  const int v[7] = {g.TC, g.gy, g.RG, g.spb, (int)g.gx, TWW, TW};
+  for (int i = 0; i < 7; ++i) out7[i] = v[i];
+  return 0;
 }
 
 // part must hold seg_dw_wgrad_blocks(N, Ho, Wo, C) * 9 * C floats; reduce with
@@ -446,11 +464,10 @@ static int dw_wgrad_impl(const T* dy, long lddy, const T* x, long ldx, int N, in
                          float* part, hipStream_t stream) {
   if ((C & 3) || (lddy & 3) || (ldx & 3) || (stride != 1 && stride != 2) || ((in_scale == nullptr) != (in_shift == nullptr)))
     return (int)hipErrorInvalidValue;
-  int TC, gy, spb;
-  long gx;
-  wgrad_tiling(C, &TC, &gy);
-  wgrad_grid(N, Ho, Wo, C, &gx, &spb);
-  const size_t lds = (size_t)(256 / TC) * TC * 9 * sizeof(f32x4);
+  const WgradGeo geo = wgrad_geo(N, Ho, Wo, C);
+  const int TC = geo.TC, gy = geo.gy, spb = geo.spb;
+  const long gx = geo.gx;
+  const size_t lds = (size_t)geo.RG * TC * 9 * sizeof(f32x4);
   const bool lazy = in_scale != nullptr;
 #define SEG_DW_WG(S, L)                                                                                         \
   hipLaunchKernelGGL((dw_wgrad_kernel<S, L, T>), dim3(gx * gy), dim3(256), lds, stream, dy, lddy, x, ldx, N, H, W, C, \

@@ -60,6 +60,7 @@ PROTOTYPES = {
     "seg_dw_fwd_bias_act": (_I, [_V, _L, _I, _I, _I, _I, _V, _V, _I, _V, _L, _I, _I, _I, _V]),
     "seg_dw_dgrad": (_I, [_V, _L, _I, _I, _I, _I, _V, _V, _L, _I, _I, _I, _I, _V]),
     "seg_dw_wgrad_blocks": (_L, [_I, _I, _I, _I]),
+    "seg_dw_wgrad_geometry": (_I, [_I, _I, _I, _I, _V]),
     "seg_dw_wgrad": (_I, [_V, _L, _V, _L, _I, _I, _I, _I, _V, _V, _I, _I, _I, _I, _V, _V]),
     "seg_nchw_to_nhwc": (_I, [_V, _I, _I, _I, _I, _V, _I, _V]),
     "seg_chan_workspace_floats": (_L, [_L, _I]),
