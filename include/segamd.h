@@ -648,6 +648,55 @@ int seg_temporal_argmax_nearest(const float* low, long ld, int N, int H, int W, 
                                 int fallback_class, unsigned char* labels, unsigned char* mask, int Hf, int Wf,
                                 hipStream_t stream);
 
+/* ---- test-time augmentation: flip / multi-scale ensembles (csrc/tta.h, tta.hip, infer.hip) ----
+ * A view is a forward of a resized and / or mirrored copy of the same images.  Its low-resolution NHWC
+ * logits `low` [N][H][W][ld] (image n at low + n*H*W*ld; pad lanes C..ld-1 never used; 16-byte aligned,
+ * ld % 4 == 0, ld >= C) map onto the model's Ho x Wo output grid as the model's final align_corners=True
+ * upsample maps them (source coordinate and tap index in fp32: one interpolation, whatever the view's
+ * size); a mirrored view (flip != 0) is read at x_v = Wo - 1 - x.  Per output pixel, in fp32:
+ *   z_v = the blend of the view's four taps,  p = sum_v w_v * softmax(z_v),  class = first maximum of p,
+ * with w_v = weight_v / sum of the weights (every weight positive and finite).  The entry points take a
+ * HOST array of 1..SEG_TTA_MAX_VIEWS descriptors and pass it to their kernels by value: no device
+ * allocation, no copy, capturable in a graph.  Anything else: hipErrorInvalidValue before any launch. */
+#define SEG_TTA_MAX_VIEWS 8
+typedef struct seg_tta_view {
+  const float* low;
+  long ld;
+  int H, W;
+  int flip;
+  float weight;
+} seg_tta_view;
+/* out [N][C][Hv][Wv] = flip(F.interpolate(x [N][C][H][W], (Hv, Wv), mode="bilinear", align_corners=False),
+ * -1) when flip != 0, the resize alone otherwise (fp32 NCHW; a view of x's own size is a copy / mirror). */
+int seg_tta_view_nchw(const float* x, int N, int C, int H, int W, float* out, int Hv, int Wv, int flip,
+                      hipStream_t stream);
+/* seg_preprocess_bgr of ONE frame into `copies` (1..8) images out[copies*H*W][ld]: image i is mirrored
+ * left-right when bit i of flip_mask is set, its pixel (y, x) bitwise seg_preprocess_bgr's at (y, W-1-x). */
+int seg_preprocess_bgr_views(const unsigned char* frame, int Hf, int Wf, long row_bytes, float* out, int ld,
+                             int H, int W, int copies, int flip_mask, float mean_r, float mean_g, float mean_b,
+                             float std_r, float std_g, float std_b, hipStream_t stream);
+/* The ensemble's validation step in one kernel (+ a finalize): loss = nn.NLLLoss(class_weight, ignore_index,
+ * reduction)(log p, labels) and confusion[label * C + class] += 1 for every valid pixel.  views: const
+ * seg_tta_view[nviews]; labels int64 [N][Ho][Wo]; class_weight C device floats or NULL; reduction 0 = mean,
+ * 1 = sum; work >= seg_tta_workspace_floats(N*Ho*Wo) floats; out4 = [loss, D, #out-of-range labels, #valid
+ * pixels] as seg_cew_upsample_eval's (an out-of-range label makes the loss NaN); confusion int64 [C][C], added
+ * to; prob NULL or fp32 [N][C][Ho][Wo], which receives p at every pixel.  C in 1..32.  labels == NULL (prob given):
+ * probabilities only -- every pixel counts as ignored and confusion may be NULL too.  A non-finite logit
+ * gets no special case: the loss becomes non-finite and the pixel is binned under some class in [0, C).
+ * Per-block partials and a fixed-order finalize, integer atomics for the matrix: two runs are bitwise equal. */
+long seg_tta_workspace_floats(long pixels);
+int seg_tta_upsample_eval(const void* views, int nviews, int N, int C, const long long* labels, int Ho, int Wo,
+                          int ignore_index, const float* class_weight, int reduction, float* work, float* out4,
+                          long long* confusion, float* prob, hipStream_t stream);
+/* seg_argmax_nearest on the ensemble: state [N*Hm*Wm][lds] (seg_temporal_argmax_nearest's layout; pad lanes of
+ * the written quads 0) receives p, labels [N][Hm][Wm] its classes -- fallback_class where the largest p <
+ * min_conf -- and mask [N][Hf][Wf] their cv2 INTER_NEAREST.  A view whose z_v is non-finite at a pixel is left
+ * out there and the remaining weights are renormalised; none left: p = 1/C.  C in 1..255.  Two launches, no
+ * atomics: the same values eagerly and in a replayed graph. */
+int seg_tta_argmax_nearest(const void* views, int nviews, int N, int C, int Hm, int Wm, float* state, int lds,
+                           float min_conf, int fallback_class, unsigned char* labels, unsigned char* mask, int Hf,
+                           int Wf, hipStream_t stream);
+
 /* ---- GPU augmentation (the readers' albumentations pipeline,
  *      src/BDD100KDataset.py:38-52) ---------------------- */
 /* Resize a batch [N][Hs][src_row] of uint8 images (C = 3: cv2 INTER_LINEAR 8-bit)

@@ -26,6 +26,7 @@
 // double.  Parity of these two against real cv2 is unpinned (oracle/cvresize.py
 // restates the same arithmetic; tests pin kernel == restatement bit-exactly).
 #include "common.h"
+#include "tta.h"
 
 #ifndef SEG_ARGMAX_BAND
 #define SEG_ARGMAX_BAND 1
@@ -387,12 +388,12 @@ __global__ __launch_bounds__(64) void temporal_update_kernel(const float* __rest
 // mask[n][yf][xf] = labels[n][nearest model pixel] (cv2 INTER_NEAREST, as argmax_nearest_kernel's): a block
 // per frame row (blockIdx.x = n * Hf + yf, its model row found once), a thread per kPix pixels of it: four
 // per 32-bit store (Wf % 4 == 0, host check) or one.  Runs after temporal_update_kernel in stream order and
-// clears the fresh word that kernel read.
+// clears the fresh word that kernel read (fresh == NULL: the test-time-augmentation path, which has none).
 template <int kPix>
 __global__ __launch_bounds__(256) void labels_nearest_kernel(const uint8_t* __restrict__ labels, int Hm, int Wm,
                                                              uint8_t* __restrict__ mask, int Hf, int Wf, double ify,
                                                              double ifx, int* __restrict__ fresh) {
-  if (blockIdx.x == 0 && threadIdx.x == 0) *fresh = 0;
+  if (fresh && blockIdx.x == 0 && threadIdx.x == 0) *fresh = 0;
   const int n = blockIdx.x / Hf, yf = blockIdx.x - n * Hf;
   const uint8_t* lr = labels + ((long)n * Hm + nearest_src(yf, ify, Hm)) * Wm;
   uint8_t* out = mask + (long)blockIdx.x * Wf;
@@ -405,6 +406,118 @@ __global__ __launch_bounds__(256) void labels_nearest_kernel(const uint8_t* __re
     } else {
       out[x] = lr[nearest_src(x, ifx, Wm)];
     }
+  }
+}
+
+// ---------------------------------------------------------------- test-time augmentation
+// One frame -> `copies` images of NHWC rows (the Predictor's views of one size, a batch): image i mirrored
+// when bit i of flip_mask is set -- its pixel (y, x) is pre_pixel's at (y, W - 1 - x), bit for bit.
+__global__ __launch_bounds__(256) void preprocess_bgr_views_kernel(const uint8_t* __restrict__ frame, long row_bytes,
+                                                                   int Hf, int Wf, float* __restrict__ out, int ld,
+                                                                   int H, int W, int copies, unsigned flip_mask,
+                                                                   double scale_x, double scale_y, float m0, float m1,
+                                                                   float m2, float s0, float s1, float s2) {
+  const long total = (long)copies * H * W;
+  for (long p = blockIdx.x * 256L + threadIdx.x; p < total; p += (long)gridDim.x * 256) {
+    const int i = (int)(p / ((long)H * W));
+    const int rem = (int)(p - (long)i * H * W);
+    const int dy = rem / W, dx = rem - dy * W;
+    const int sx = (flip_mask >> i) & 1u ? W - 1 - dx : dx;
+    st4(out + p * ld, pre_pixel(frame, row_bytes, Hf, Wf, dy, sx, scale_x, scale_y, m0, m1, m2, s0, s1, s2));
+  }
+}
+
+// The ensemble's class per MODEL pixel (tta.h): p = sum_v w_v softmax(z_v) over the views whose z_v is finite
+// at the pixel, the weights of the others renormalised away (none left: p = 1/C); state row = p (pad lanes of
+// the written quads 0); label = the first maximum of p, or `fallback` below min_conf.  One thread per pixel,
+// as temporal_update_kernel.  NQ > 0: p's NQ quads stay in registers; NQ == 0: any C, the pixel's own state
+// row is the accumulator (written by the first finite view, added to by the others, scaled in a last pass).
+template <int NQ>
+__global__ __launch_bounds__(64) void tta_classify_kernel(const TtaTable t, int N, int C, int Hm, int Wm,
+                                                          float* __restrict__ state, int lds, float min_conf,
+                                                          int fallback, uint8_t* __restrict__ labels) {
+  constexpr int kQ = NQ ? NQ : 1;
+  const int nq = NQ ? NQ : (C + 3) >> 2;
+  const float uniform = 1.f / (float)C;
+  const long total = (long)N * Hm * Wm;
+  for (long px = blockIdx.x * 64L + threadIdx.x; px < total; px += (long)gridDim.x * 64) {
+    const int n = (int)(px / ((long)Hm * Wm));
+    const int rem = (int)(px - (long)n * Hm * Wm);
+    const int ym = rem / Wm, xm = rem - ym * Wm;
+    float* srow = state + px * lds;
+    f32x4 p[kQ];
+    float wsum = 0.f;
+    int used = 0;
+    if constexpr (NQ > 0) {
+#pragma unroll
+      for (int q = 0; q < NQ; ++q) p[q] = f32x4{0.f, 0.f, 0.f, 0.f};
+      for (int v = 0; v < t.n; ++v) {  // wave-uniform
+        const float w = tta_accumulate<NQ, true>(t.v[v], n, ym, xm, Wm, C, p);
+        wsum += w;
+        used += w > 0.f;
+      }
+    } else {
+      for (int v = 0; v < t.n; ++v) {
+        const TtaView& tv = t.v[v];
+        const TtaTaps tp = tta_taps(tv, n, ym, xm, Wm);
+        float zmax = -__builtin_inff();
+        bool finite = true;
+        for (int q = 0; q < nq; ++q) {
+          const f32x4 z = tta_blend(tp, q);
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            if (4 * q + j >= C) continue;
+            finite = finite && fabsf(z[j]) < __builtin_inff();
+            zmax = fmaxf(zmax, z[j]);
+          }
+        }
+        if (!finite) continue;
+        float sum = 0.f;
+        for (int q = 0; q < nq; ++q) {
+          const f32x4 z = tta_blend(tp, q);
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            if (4 * q + j < C) sum += expf(z[j] - zmax);
+        }
+        const float ws = tv.weight / sum;
+        for (int q = 0; q < nq; ++q) {
+          const f32x4 z = tta_blend(tp, q);
+          f32x4 s = {0.f, 0.f, 0.f, 0.f};
+          if (used) s = ld4(srow + 4 * q);
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            s[j] = 4 * q + j < C ? __builtin_fmaf(expf(z[j] - zmax), ws, s[j]) : 0.f;
+          st4(srow + 4 * q, s);
+        }
+        wsum += tv.weight;
+        used += 1;
+      }
+    }
+    // every view taken: p as it is; some left out: their weight renormalised away; none: uniform
+    const float scale = used == t.n ? 1.f : 1.f / wsum;
+    float best = 0.f;
+    int arg = 0;
+#pragma unroll kQ
+    for (int q = 0; q < nq; ++q) {
+      f32x4 s;
+      if constexpr (NQ > 0) s = p[q];
+      else s = used ? ld4(srow + 4 * q) : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int k = 4 * q + j;
+        if (k >= C) {
+          s[j] = 0.f;
+          continue;
+        }
+        s[j] = used == 0 ? uniform : (used == t.n ? s[j] : s[j] * scale);
+        if (k == 0 || s[j] > best) {
+          best = s[j];
+          arg = k;
+        }
+      }
+      st4(srow + 4 * q, s);
+    }
+    labels[px] = (uint8_t)(best < min_conf ? fallback : arg);
   }
 }
 
@@ -508,5 +621,55 @@ SEG_API int seg_temporal_argmax_nearest(const float* low, long ld, int N, int H,
   else
     hipLaunchKernelGGL(labels_nearest_kernel<1>, dim3(N * Hf), dim3(256), 0, stream, labels, Hm, Wm, mask, Hf, Wf, ify,
                        ifx, fresh);
+  SEG_RET_LAST();
+}
+
+// seg_preprocess_bgr of ONE frame into `copies` (1..8) images out[copies*H*W][ld] -- the Predictor's
+// test-time-augmentation views of one size, a batch for one folded forward; image i is mirrored left-right
+// when bit i of flip_mask is set (bitwise seg_preprocess_bgr's pixel at (y, W - 1 - x)).
+SEG_API int seg_preprocess_bgr_views(const uint8_t* frame, int Hf, int Wf, long row_bytes, float* out, int ld, int H,
+                                     int W, int copies, int flip_mask, float mean_r, float mean_g, float mean_b,
+                                     float std_r, float std_g, float std_b, hipStream_t stream) {
+  if (!frame || !out || ld < 4 || (ld & 3) || row_bytes < 3L * Wf || Hf <= 0 || Wf <= 0 || H <= 0 || W <= 0 ||
+      copies < 1 || copies > kTtaMaxViews || flip_mask < 0 || (flip_mask >> copies))
+    return (int)hipErrorInvalidValue;
+  const double scale_x = 1.0 / ((double)W / Wf), scale_y = 1.0 / ((double)H / Hf);
+  hipLaunchKernelGGL(preprocess_bgr_views_kernel, dim3(grid_for((long)copies * H * W)), dim3(256), 0, stream, frame,
+                     row_bytes, Hf, Wf, out, ld, H, W, copies, (unsigned)flip_mask, scale_x, scale_y, mean_r, mean_g,
+                     mean_b, std_r, std_g, std_b);
+  SEG_RET_LAST();
+}
+
+// seg_argmax_nearest on a test-time-augmentation ensemble: views = HOST array of nviews (1..8) seg_tta_view,
+// the low-resolution logits of the views of the same N images (tta.h); state [N*Hm*Wm][lds] receives p,
+// labels [N][Hm][Wm] its classes (fallback_class where the largest p < min_conf), mask [N][Hf][Wf] their cv2
+// INTER_NEAREST.  A view whose z is non-finite at a pixel is left out there.  Two launches, no atomics.
+SEG_API int seg_tta_argmax_nearest(const void* views, int nviews, int N, int C, int Hm, int Wm, float* state, int lds,
+                                   float min_conf, int fallback_class, uint8_t* labels, uint8_t* mask, int Hf, int Wf,
+                                   hipStream_t stream) {
+  TtaTable t;
+  if (C > 255 || N <= 0 || !tta_table(views, nviews, C, Hm, Wm, &t) || (lds & 3) || lds < C ||
+      !(min_conf >= 0.f && min_conf <= 1.f) || fallback_class < 0 || fallback_class >= C || !state || !labels ||
+      !mask || ((uintptr_t)state & 15) || Hf <= 0 || Wf <= 0 || (long)N * Hf > 0x7fffffffL)
+    return (int)hipErrorInvalidValue;
+  const double ify = 1.0 / ((double)Hf / Hm), ifx = 1.0 / ((double)Wf / Wm);
+  const dim3 grid((unsigned)std::min<long>(seg_cdiv((long)N * Hm * Wm, 64), 8192));
+#define SEG_TTA_CLASSIFY(NQ)                                                                                   \
+  hipLaunchKernelGGL(tta_classify_kernel<NQ>, grid, dim3(64), 0, stream, t, N, C, Hm, Wm, state, lds, min_conf, \
+                     fallback_class, labels)
+  switch ((C + 3) / 4) {
+    case 1: SEG_TTA_CLASSIFY(1); break;
+    case 2: SEG_TTA_CLASSIFY(2); break;
+    case 3: SEG_TTA_CLASSIFY(3); break;
+    case 4: SEG_TTA_CLASSIFY(4); break;
+    default: SEG_TTA_CLASSIFY(0); break;
+  }
+#undef SEG_TTA_CLASSIFY
+  if (Wf % 4 == 0 && ((uintptr_t)mask & 3) == 0)
+    hipLaunchKernelGGL(labels_nearest_kernel<4>, dim3(N * Hf), dim3(256), 0, stream, labels, Hm, Wm, mask, Hf, Wf, ify,
+                       ifx, (int*)nullptr);
+  else
+    hipLaunchKernelGGL(labels_nearest_kernel<1>, dim3(N * Hf), dim3(256), 0, stream, labels, Hm, Wm, mask, Hf, Wf, ify,
+                       ifx, (int*)nullptr);
   SEG_RET_LAST();
 }

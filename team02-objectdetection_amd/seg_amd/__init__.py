@@ -15,6 +15,8 @@ Public surface (drop-in for the reference's src/unet.py and src/train.py):
     grad_norm, clip_grad_norm_            (global L2 gradient norm and clipping on the device)
     EMA                                   (exponential moving average of the weights: one launch per step,
                                            exchanged in place with the live weights for evaluation)
+    TTA, view_shapes                      (test-time augmentation: flip / multi-scale ensembles for validate,
+                                           Predictor, model.forward_tta / forward_metrics_tta; one fused kernel)
     traceable                             (pure-torch CPU twin for convert.py's ONNX export)
     freeze, unfreeze, frozen_modules      (fine-tuning: frozen backbone / frozen BatchNorm statistics)
     Predictor, preprocess_image           (inference.py's per-frame path)
@@ -35,6 +37,7 @@ from .overlay import Overlay, overlay_predictions, COLOR_MAP  # noqa: F401
 from .optim import Adam, AdamW, clip_grad_norm_, decay_groups, grad_norm  # noqa: F401
 from .ema import EMA  # noqa: F401
 from .export import traceable  # noqa: F401
+from .tta import TTA, view_shapes  # noqa: F401
 from .freeze import freeze, unfreeze, frozen_modules  # noqa: F401
 
 __all__ = ["MobileNetV2UNet", "UNet", "LightUNet", "double_conv", "inconv", "down", "up", "outconv",
@@ -44,5 +47,5 @@ __all__ = ["MobileNetV2UNet", "UNet", "LightUNet", "double_conv", "inconv", "dow
            "synthetic_batch",
            "CombinedLaneDataset", "DistributedWeightedSampler", "reference_sample_weights",
            "Predictor", "preprocess_image", "Overlay", "overlay_predictions", "COLOR_MAP",
-           "Adam", "AdamW", "clip_grad_norm_", "decay_groups", "grad_norm", "EMA",
+           "Adam", "AdamW", "clip_grad_norm_", "decay_groups", "grad_norm", "EMA", "TTA", "view_shapes",
            "traceable", "freeze", "unfreeze", "frozen_modules"]

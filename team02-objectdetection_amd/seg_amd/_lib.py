@@ -108,6 +108,12 @@ PROTOTYPES = {
     "seg_preprocess_bgr": (_I, [_V, _I, _I, _I, _L, _V, _I, _I, _I, _F, _F, _F, _F, _F, _F, _V]),
     "seg_argmax_nearest": (_I, [_V, _L, _I, _I, _I, _I, _I, _I, _V, _I, _I, _V]),
     "seg_temporal_argmax_nearest": (_I, [_V, _L, _I, _I, _I, _I, _I, _I, _V, _I, _V, _F, _F, _I, _V, _V, _I, _I, _V]),
+    # test-time augmentation (csrc/tta.hip, csrc/infer.hip, seg_amd/tta.py)
+    "seg_tta_view_nchw": (_I, [_V, _I, _I, _I, _I, _V, _I, _I, _I, _V]),
+    "seg_preprocess_bgr_views": (_I, [_V, _I, _I, _L, _V, _I, _I, _I, _I, _I, _F, _F, _F, _F, _F, _F, _V]),
+    "seg_tta_workspace_floats": (_L, [_L]),
+    "seg_tta_upsample_eval": (_I, [_V, _I, _I, _I, _V, _I, _I, _I, _V, _I, _V, _V, _V, _V, _V]),
+    "seg_tta_argmax_nearest": (_I, [_V, _I, _I, _I, _I, _I, _V, _I, _F, _I, _V, _V, _I, _I, _V]),
     "seg_resize_u8": (_I, [_V, _I, _I, _I, _L, _V, _I, _I, _I, _V, _V]),
     "seg_augment": (_I, [_V, _V, _I, _I, _I, _V, _F, _F, _F, _F, _F, _F, _V, _V, _V]),
     "seg_adam_step": (_I, [_V, _V, _I, _I, _F, _F, _F, _F, _V]),

@@ -358,6 +358,15 @@ class DataParallel(nn.Module):
         return self.module.forward_metrics(x, target, confusion, ignore_index, weight, label_smoothing, reduction,
                                            **seg_loss)
 
+    def forward_tta(self, x, tta):
+        """The module's test-time-augmentation ensemble on this rank's shard (no gradients, nothing armed)."""
+        return self.module.forward_tta(x, tta)
+
+    def forward_metrics_tta(self, x, target, confusion, tta, ignore_index: int = -100, weight=None,
+                            reduction: str = "mean"):
+        """forward_metrics of the ensemble on this rank's shard; seg_amd.validate's all-reduces are the same."""
+        return self.module.forward_metrics_tta(x, target, confusion, tta, ignore_index, weight, reduction)
+
     def state_dict(self, *args, **kwargs):
         return self.module.state_dict(*args, **kwargs)
 

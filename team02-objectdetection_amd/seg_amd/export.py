@@ -53,8 +53,8 @@ def _check(x):
                            "model itself (the HIP path)")
 
 
-def mobilenet_unet_forward(m, x):
-    """MobileNetV2UNet.forward (src/unet.py:32-51) over m's own modules, in torch ops."""
+def mobilenet_unet_low_logits(m, x):
+    """MobileNetV2UNet.forward in front of its final upsample: the logits at half resolution."""
     x1 = _stage(m.down1, x)
     x2 = _stage(m.down2, x1)
     x3 = _stage(m.down3, x2)
@@ -64,7 +64,12 @@ def mobilenet_unet_forward(m, x):
     x = _up(m.up2, x, x3)
     x = _up(m.up3, x, x2)
     x = _up(m.up4, x, x1)
-    return m.final_upsample(m.outc.conv(x))
+    return m.outc.conv(x)
+
+
+def mobilenet_unet_forward(m, x):
+    """MobileNetV2UNet.forward (src/unet.py:32-51) over m's own modules, in torch ops."""
+    return m.final_upsample(mobilenet_unet_low_logits(m, x))
 
 
 def unet_forward(m, x):
@@ -85,6 +90,14 @@ def torch_forward(model, x):
     BASELINE configs[0]); CUDA input always runs the HIP engine (unet._SegModel.forward)."""
     _check(x)
     return mobilenet_unet_forward(model, x) if isinstance(model, MobileNetV2UNet) else unet_forward(model, x)
+
+
+def torch_low_logits(model, x):
+    """The logits in front of `model`'s final upsample as an NCHW tensor, in torch ops (CPU tensors): the first half
+    of torch_forward for a MobileNetV2UNet, all of it for a UNet / LightUNet, which have no final upsample.  What the
+    test-time-augmentation ensemble (seg_amd/tta.py) samples on the CPU."""
+    _check(x)
+    return mobilenet_unet_low_logits(model, x) if isinstance(model, MobileNetV2UNet) else unet_forward(model, x)
 
 
 class TorchMobileNetV2UNet(MobileNetV2UNet):

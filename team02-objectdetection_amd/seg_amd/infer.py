@@ -16,13 +16,17 @@ captured once into a HIP graph (torch.cuda.CUDAGraph drives hipGraph on ROCm):
     seg_argmax_nearest      final align_corners=True upsample + argmax + nearest
                             resize to the frame -> uint8 class mask
                             (seg_temporal_argmax_nearest with `temporal=` / `min_confidence=`:
-                            the argmax of the class probabilities averaged over the frames)
+                            the argmax of the class probabilities averaged over the frames;
+                            seg_tta_argmax_nearest with `tta=`: the argmax of the probabilities averaged
+                            over the flipped / rescaled views, behind seg_preprocess_bgr_views and one
+                            folded forward per view size)
 
 `preprocess_image` mirrors inference.py's function of the same name (same
 argument meaning and return values) for callers that still want the tensor.
 """
 from __future__ import annotations
 
+import ctypes
 import numbers
 
 import numpy as np
@@ -101,11 +105,32 @@ class Predictor:
     graph too); min_confidence > 0 paints pixels whose largest averaged probability is below it with
     fallback_class.  Either option switches the path on (alpha 1.0 when only min_confidence is given).
     `reset()` starts a new average (scene cut, seek); `probabilities()` / `confidence()` read it.
+
+    tta (a seg_amd.TTA, or "hflip") classifies the frame from a test-time-augmentation ensemble (seg_amd/tta.py has
+    the definition): every view is formed straight from the frame at its own size (seg_preprocess_bgr_views: nothing
+    is resized twice), the plain and the mirrored view of one size run as ONE batch-2 folded forward (inference is
+    launch-bound at batch 1), and seg_tta_argmax_nearest replaces seg_argmax_nearest, inside the graph too.
+    min_confidence / fallback_class act on the ensemble's p as they act on the temporal average, and
+    `probabilities()` / `confidence()` read p; a view whose logits are non-finite at a pixel is left out there.
+    tta_batch=False runs every view as a batch-1 forward of its own instead -- what math="f16" always does: its
+    fused inverted-residual launches are batch-1 routes, so tta_batch=True is a ValueError there.  tta together
+    with temporal is a ValueError.
     """
 
     def __init__(self, model, frame_hw=(720, 1280), target_size=(256, 128), graph: bool = True, math: str = "f32",
-                 overlay=False, temporal: float | None = None, min_confidence: float = 0.0, fallback_class: int = 0):
+                 overlay=False, temporal: float | None = None, min_confidence: float = 0.0, fallback_class: int = 0,
+                 tta=None, tta_batch: bool | None = None):
         temporal_options(temporal, min_confidence, fallback_class)  # bad values: ValueError before anything else
+        from .tta import as_tta
+        self.tta = as_tta(tta)
+        if self.tta is not None and temporal is not None:
+            raise ValueError("Predictor tta and temporal cannot be combined: averaging the ensemble's probabilities "
+                             "over the frames is not implemented")
+        if tta_batch is not None and not isinstance(tta_batch, bool):
+            raise ValueError(f"Predictor tta_batch must be None or a bool, got {tta_batch!r}")
+        if self.tta is not None and tta_batch and math == "f16":
+            raise ValueError("Predictor tta_batch=True is not available with math='f16': its fused folded routes "
+                             "(seg_mbconv_f16, seg_pw2_f16) run at batch 1 only")
         p = next(model.parameters())
         if not p.is_cuda:
             raise RuntimeError("Predictor runs on the MI355X HIP path only; move the model to 'cuda' first")
@@ -117,22 +142,33 @@ class Predictor:
         # (BASELINE configs[3]: fp16 operands, fp32 accumulation) or "bf16"
         if math not in ("f32", "f16", "bf16"):
             raise ValueError(f"Predictor math must be 'f32', 'f16' or 'bf16', got {math!r}")
-        self.prog = get_program(model, 1, self.H, self.W, math)
         self.frame = torch.zeros((self.Hf, self.Wf, 3), device=self.device, dtype=torch.uint8)
         self.mask = torch.empty((self.Hf, self.Wf), device=self.device, dtype=torch.uint8)
-        self.run = Run(self.prog, self.frame, training=False)
+        self.run = None
+        if self.tta is None:
+            self.prog = get_program(model, 1, self.H, self.W, math)
+            self.run = Run(self.prog, self.frame, training=False)
+        else:
+            self._tta_setup(model, math, math != "f16" if tta_batch is None else tta_batch)
+            # the output grid and the class count are the scale-1 program's: a view group's own when one has that
+            # size (whatever its batch), else a program built for them alone (no buffers: it never runs)
+            same = [g[1] for g in self._tta_groups if (g[1].image.H, g[1].image.W) == (self.H, self.W)]
+            self.prog = same[0] if same else get_program(model, 1, self.H, self.W, math)
         self.classes = self.prog.logits.C
         self.temporal = temporal_options(temporal, min_confidence, fallback_class, self.classes)
+        if self.tta is not None and self.temporal is None:
+            self.temporal = (1.0, 0.0, 0)  # the state, labels and readers of the smoothing path; no threshold
         if self.temporal is not None:
             Ho, Wo = self.prog.out_hw
             lds = (self.classes + 3) // 4 * 4
-            # the average [Ho*Wo][lds], the word that starts a new one, the classes at model resolution
+            # the average [Ho*Wo][lds], the word that starts a new one (not with tta), the classes at model resolution
             self._state = torch.zeros((Ho * Wo, lds), device=self.device, dtype=torch.float32)
-            self._fresh = torch.ones(1, device=self.device, dtype=torch.int32)
+            if self.tta is None:
+                self._fresh = torch.ones(1, device=self.device, dtype=torch.int32)
             self._labels = torch.zeros((Ho, Wo), device=self.device, dtype=torch.uint8)
         self.graph = None
         self.refresh()
-        self.stem_pre = self.prog.stem_pre() if (engine.STEM_PRE and math == "f16") else None
+        self.stem_pre = self.prog.stem_pre() if (engine.STEM_PRE and math == "f16" and self.tta is None) else None
         self.overlay = None
         if overlay is not False and overlay is not None:
             from .overlay import Overlay
@@ -141,17 +177,63 @@ class Predictor:
                 raise ValueError(f"overlay must be True or an Overlay for {self.Hf}x{self.Wf} frames")
         if graph:
             self._capture()
-            if self.temporal is not None:
+            if self.temporal is not None and self.tta is None:
                 self.reset()  # the warm-up launch of the capture averaged the empty frame buffer
 
     def refresh(self):
         """Re-fold BatchNorm into the conv weights (after weights/statistics change)."""
         with torch.no_grad():
-            self.prog.fold(torch.cuda.current_stream(self.device).cuda_stream)
+            s = torch.cuda.current_stream(self.device).cuda_stream
+            if self.tta is None:
+                self.prog.fold(s)
+            else:
+                for prog in {id(g[1]): g[1] for g in self._tta_groups}.values():  # every view size's program
+                    prog.fold(s)
+
+    def _tta_setup(self, model, math, batch):
+        """One folded-forward group per view size (batch: its plain and mirrored view as one batch) or per view:
+        (Run, Program, copies, flip_mask); the views' order and weights are TTA.views()."""
+        from .tta import view_shapes
+        shapes = view_shapes(model, self.H, self.W, self.tta)
+        self._tta_weights = [w for _, _, _, w in shapes]
+        self._tta_groups = []
+        k = 0
+        while k < len(shapes):
+            Hv, Wv, flip, _ = shapes[k]
+            n = 2 if batch and k + 1 < len(shapes) and shapes[k + 1][:2] == (Hv, Wv) else 1
+            mask = sum(int(shapes[k + i][2]) << i for i in range(n))
+            prog = get_program(model, n, Hv, Wv, math)
+            self._tta_groups.append((Run(prog, self.frame, training=False), prog, n, mask))
+            k += n
+
+    def _launch_tta(self, s):
+        from .tta import SegTtaView
+        views = (SegTtaView * len(self._tta_weights))()
+        k = 0
+        for rt, prog, n, mask in self._tta_groups:
+            rt.stream = s
+            img, lo = prog.image, prog.logits
+            call("seg_preprocess_bgr_views", self.frame.data_ptr(), self.Hf, self.Wf, self.frame.stride(0),
+                 rt.ptr(img), img.ld, img.H, img.W, n, mask, *MEAN, *STD, s)
+            rt.forward_folded()
+            for i in range(n):
+                v = views[k]
+                v.low, v.ld, v.H, v.W = rt.ptr(lo) + 4 * i * lo.H * lo.W * lo.ld, lo.ld, lo.H, lo.W
+                v.flip, v.weight = (mask >> i) & 1, self._tta_weights[k]
+                k += 1
+        Ho, Wo = self.prog.out_hw
+        _, min_conf, fallback = self.temporal
+        call("seg_tta_argmax_nearest", ctypes.addressof(views), len(views), 1, self.classes, Ho, Wo,
+             self._state.data_ptr(), self._state.shape[1], min_conf, fallback, self._labels.data_ptr(),
+             self.mask.data_ptr(), self.Hf, self.Wf, s)
+        if self.overlay is not None:
+            self.overlay.launch(self.frame, self.mask, s)
 
     def _launch(self):
-        rt, prog = self.run, self.prog
         s = torch.cuda.current_stream(self.device).cuda_stream
+        if self.tta is not None:
+            return self._launch_tta(s)
+        rt, prog = self.run, self.prog
         rt.stream = s
         img = prog.image
         if self.stem_pre is not None:  # preprocess formed on load by the stem conv (seg_stem_pre_f16)
@@ -223,14 +305,15 @@ class Predictor:
     def reset(self):
         """Start a new average with the next frame (a scene cut, a seek): sets the device word the update
         kernel reads, in stream order; the captured graph stays as it is.  refresh() does not reset."""
-        if self.temporal is None:
-            raise RuntimeError("reset() needs Predictor(..., temporal=alpha) or min_confidence > 0")
+        if self.temporal is None or self.tta is not None:
+            raise RuntimeError("reset() needs Predictor(..., temporal=alpha) or min_confidence > 0, without tta")
         self._fresh.fill_(1)
 
     def probabilities(self) -> torch.Tensor:
-        """[1, C, H, W] float32 view of the averaged class probabilities s_t after the last frame."""
+        """[1, C, H, W] float32 view of the averaged class probabilities s_t after the last frame (with tta: of the
+        ensemble's p)."""
         if self.temporal is None:
-            raise RuntimeError("probabilities() needs Predictor(..., temporal=alpha) or min_confidence > 0")
+            raise RuntimeError("probabilities() needs Predictor(..., temporal=alpha), min_confidence > 0 or tta")
         Ho, Wo = self.prog.out_hw
         return self._state.view(1, Ho, Wo, -1)[..., :self.classes].permute(0, 3, 1, 2)
 
@@ -240,6 +323,8 @@ class Predictor:
 
     def logits(self) -> torch.Tensor:
         """[1, C, H, W] logits of the last frame (the model's return value, src/unet.py:49)."""
+        if self.tta is not None:
+            raise RuntimeError("logits() has no meaning for a tta ensemble of several views; read probabilities()")
         lo = self.prog.logits
         Ho, Wo = self.prog.out_hw
         out = torch.empty((1, lo.C, Ho, Wo), device=self.device, dtype=torch.float32)

@@ -235,7 +235,20 @@ def _num_classes(core) -> int:
     return convs[-1].out_channels
 
 
-def validate(model, val_loader, criterion, device, progress: bool = True, epoch: int = 0, epochs: int = 1) -> dict:
+def tta_loss_options(criterion):
+    """The hard term of `criterion` as forward_metrics_tta's keyword arguments: class weights, ignore_index and
+    reduction ("mean" unless an nn.CrossEntropyLoss asks for "sum").  Label smoothing, Dice, focal and OHEM terms
+    shape training, not an ensemble's report, and are left out -- the rule validate() already applies to a
+    DistillLoss.  ValueError for a criterion that is none of the fused ones (fused_loss_options)."""
+    if fused_loss_options(criterion) is None:
+        raise ValueError("validate(tta=...) takes an nn.CrossEntropyLoss (reduction 'mean' or 'sum'), a seg_amd.SegLoss, "
+                         f"OhemCELoss or DistillLoss, got {type(criterion).__name__}")
+    reduction = criterion.reduction if isinstance(criterion, nn.CrossEntropyLoss) else "mean"
+    return {"ignore_index": criterion.ignore_index, "weight": criterion.weight, "reduction": reduction}
+
+
+def validate(model, val_loader, criterion, device, progress: bool = True, epoch: int = 0, epochs: int = 1,
+             tta=None) -> dict:
     """One pass over `val_loader` in eval mode, without gradients: the reference's disabled
     validation phase (src/train.py:46-66) plus the metrics of seg_amd.metrics.summarize.
 
@@ -255,14 +268,28 @@ def validate(model, val_loader, criterion, device, progress: bool = True, epoch:
 
     A seg_amd.DistillLoss is evaluated as its hard() term, nn.CrossEntropyLoss(weight, ignore_index): the student's
     validation loss is a hard-label quantity (train_model's best_checkpoint compares it) and no teacher forward
-    runs."""
+    runs.
+
+    tta (a seg_amd.TTA, or "hflip"): every batch is evaluated as a test-time-augmentation ensemble,
+    model.forward_metrics_tta (seg_amd/tta.py has the definition): loss = NLLLoss(log p) of the averaged class
+    probabilities, the matrix from their argmax.  Any fused criterion is then evaluated as its HARD term -- class
+    weights, ignore_index, reduction (tta_loss_options): label smoothing, Dice, focal and OHEM terms shape training,
+    not an ensemble's report.  Everything else -- the one host wait, the IndexError, the two all-reduces -- is as
+    without it; tta=None runs every line of the path above as it always did."""
     from .losses import DistillLoss
     from .metrics import add_confusion, summarize
     if isinstance(criterion, DistillLoss):
         criterion = criterion.hard()  # validation does not distil: hard-label loss and mIoU, no teacher forward
     core = getattr(model, "module", model)
     ignore_index = getattr(criterion, "ignore_index", -100)
-    opts = fused_loss_options(criterion) if hasattr(core, "forward_metrics") else None
+    if tta is not None:
+        from .tta import as_tta
+        tta = as_tta(tta)
+        if not hasattr(core, "forward_metrics_tta"):
+            raise ValueError(f"validate(tta=...) needs a seg_amd model, got {type(core).__name__}")
+        opts = tta_loss_options(criterion)
+    else:
+        opts = fused_loss_options(criterion) if hasattr(core, "forward_metrics") else None
     fused = opts is not None
     it = val_loader
     if progress and tqdm is not None and _is_rank0():
@@ -282,7 +309,10 @@ def validate(model, val_loader, criterion, device, progress: bool = True, epoch:
                     if confusion is None:
                         C = _num_classes(core)
                         confusion = torch.zeros((C, C), dtype=torch.int64, device=inputs.device)
-                    loss = model.forward_metrics(inputs, targets, confusion, **opts)
+                    if tta is not None:
+                        loss = model.forward_metrics_tta(inputs, targets, confusion, tta, **opts)
+                    else:
+                        loss = model.forward_metrics(inputs, targets, confusion, **opts)
                     if inputs.is_cuda:  # the CPU composition's F.cross_entropy raises by itself
                         from .engine import bad_label_count
                         acc[2] += bad_label_count(model)[0]
@@ -318,7 +348,7 @@ def train_model(model, train_loader, criterion, optimizer, device, epochs=10,
                 checkpoint_pattern: str | None = "Models/obj/obj_MOB_1_epoch_{epoch}.pth", progress: bool = True,
                 augment=None, val_loader=None, best_checkpoint: str | None = None, freeze=None,
                 freeze_epochs: int | None = None, max_grad_norm: float | None = None, ema=None,
-                ema_checkpoint_pattern: str | None = None):
+                ema_checkpoint_pattern: str | None = None, val_tta=None):
     """Train for `epochs` epochs (src/train.py:6-79).  With `val_loader`, each epoch ends with the
     reference's validation phase (commented out there, src/train.py:46-76): validate(), the
     epoch's result lines, and on an improved validation loss a state_dict at `best_checkpoint`
@@ -335,7 +365,10 @@ def train_model(model, train_loader, criterion, optimizer, device, epochs=10,
     ema.averaged_state_dict(); `ema_checkpoint_pattern` (formatted like `checkpoint_pattern`), if given, receives
     the averaged weights every epoch.  `checkpoint_pattern`'s file keeps the live weights.  Under DataParallel every
     rank keeps its own EMA (averaged gradients and broadcast BatchNorm statistics keep them equal without a
-    collective) and rank 0 writes the files.  One line at the start says which weights validation uses."""
+    collective) and rank 0 writes the files.  One line at the start says which weights validation uses.
+
+    val_tta: validate()'s tta -- the per-epoch validation (and so best_checkpoint's comparison) evaluates the
+    flip / multi-scale ensemble; with `ema` it is the ensemble of the averaged weights."""
     from .freeze import freeze as _freeze, unfreeze as _unfreeze
     from .losses import DistillLoss
     if isinstance(criterion, DistillLoss) and _is_rank0():
@@ -370,7 +403,8 @@ def train_model(model, train_loader, criterion, optimizer, device, epochs=10,
         val = None
         if val_loader is not None:  # every rank: validate() all-reduces
             with ema.applied() if ema is not None else contextlib.nullcontext():
-                val = validate(model, val_loader, criterion, device, progress, epoch, epochs)
+                kw = {} if val_tta is None else {"tta": val_tta}  # None: the call as it always was
+                val = validate(model, val_loader, criterion, device, progress, epoch, epochs, **kw)
         if _is_rank0():
             if val is not None:
                 print(f"\nEpoch {epoch + 1}/{epochs}:")

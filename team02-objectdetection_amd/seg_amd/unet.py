@@ -145,6 +145,32 @@ class _SegModel(nn.Module):
         return run_metrics(self, x, target, confusion, ignore_index, weight, label_smoothing, reduction, ce, dice,
                            focal_gamma, dice_smooth, ohem_thresh, ohem_min_kept)
 
+    def forward_tta(self, x: torch.Tensor, tta) -> torch.Tensor:
+        """The class probabilities p [N, C, H, W] (float32) of a test-time-augmentation ensemble, without gradients:
+        tta is a seg_amd.TTA or "hflip" (seg_amd/tta.py has the definition).  p = sum_v w_v softmax(z_v) over the
+        flipped / rescaled views, every z_v taken from its view's low-resolution logits by ONE interpolation to the
+        output grid.  On the MI355X each view is one forward-only pass in front of the final upsample and one kernel
+        forms p (seg_tta_upsample_eval); the views' full-resolution logits are never stored."""
+        if x.device.type == "cpu":
+            from .tta import torch_forward_tta
+            return torch_forward_tta(self, x, tta)
+        from .tta import run_forward_tta
+        return run_forward_tta(self, x, tta)
+
+    def forward_metrics_tta(self, x: torch.Tensor, target: torch.Tensor, confusion: torch.Tensor, tta,
+                            ignore_index: int = -100, weight=None, reduction: str = "mean") -> torch.Tensor:
+        """forward_metrics on the ensemble of forward_tta: returns nn.NLLLoss(weight, ignore_index, reduction)(log p,
+        target) and adds every non-ignored pixel to `confusion[label, first maximum of p]`.  Only a criterion's hard
+        term has a meaning for an ensemble's report -- class weights, ignore_index, reduction "mean" | "sum"; label
+        smoothing, Dice, focal and OHEM terms shape training and are not taken.  On the MI355X the loss, the argmax
+        and the matrix come from one kernel (seg_tta_upsample_eval) behind the views' forwards; an out-of-range label
+        makes the loss NaN and is counted for engine.bad_label_count, as in forward_metrics."""
+        if x.device.type == "cpu":
+            from .tta import torch_metrics_tta
+            return torch_metrics_tta(self, x, target, confusion, tta, ignore_index, weight, reduction)
+        from .tta import run_metrics_tta
+        return run_metrics_tta(self, x, target, confusion, tta, ignore_index, weight, reduction)
+
 
 @torch.no_grad()
 def _torch_metrics(model, x, target, confusion, ignore_index, weight=None, label_smoothing=0.0, reduction="mean",
