@@ -438,7 +438,10 @@ int seg_maxpool2_bwd(const float* in, long ldin, const float* dout, long lddout,
  * out2 = [loss, #non-ignored pixels, #labels outside [0, C) that are not
  * ignore_index] (3 floats; despite the name).  Out-of-range labels (aten raises
  * "Target out of bounds") make the loss and every gradient NaN; the caller raises
- * when it reads them (seg_amd.engine.check_targets). */
+ * when it reads them (seg_amd.engine.check_targets).
+ * hipErrorInvalidValue before any launch, for these and the seg_cew_* entry points as for
+ * every fused-loss family: C outside [1, 32], ld (ldh) % 4 != 0, ld < C, ldh < C (the kernels
+ * read and write round4(C) floats per row), or (_eval) confusion NULL. */
 long seg_ce_workspace_floats(long pixels);
 int seg_ce_upsample_loss(const float* low, long ld, int N, int H, int W, int C,
                          const long long* labels, int Ho, int Wo, int ignore_index,

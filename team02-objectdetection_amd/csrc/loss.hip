@@ -1,39 +1,46 @@
-// Per-pixel cross-entropy fused with the model's final align_corners=True
-// bilinear x2 upsample.
+// The fused segmentation losses: per-pixel criteria fused with the model's final align_corners=True
+// bilinear upsample.  Five kernel families share one file and one set of per-pixel helpers:
+//   seg_ce_*    nn.CrossEntropyLoss() as the reference applies it (main.py:99, src/train.py:37) to the model
+//               output, whose last op is final_upsample (src/unet.py:30,49): weight=None, ignore_index=-100,
+//               label_smoothing=0, labels int64.  loss = sum_{valid p} (logsumexp(z_p) - z_p[y_p]) / #valid,
+//               d loss / d z_p = g * (softmax(z_p) - onehot(y_p)) / #valid  (g = upstream grad).
+//   seg_cew_*   aten's remaining options for class-index targets: class weights, label smoothing, mean / sum.
+//   seg_sl_*    a focal term and soft Dice beside cross-entropy (seg_amd.SegLoss).
+//   seg_ohem_*  online hard example mining (seg_amd.OhemCELoss).
+//   seg_kd_*    knowledge distillation from a teacher's logits (seg_amd.DistillLoss).
+// Each family's formulas stand above its kernels.
 //
-// Reference: criterion = nn.CrossEntropyLoss() (main.py:99) applied to the model
-// output (src/train.py:37), whose last op is final_upsample (src/unet.py:30,49).
-// Semantics: loss = sum_{valid p} (logsumexp(z_p) - z_p[y_p]) / #valid,
-// weight=None, ignore_index=-100, label_smoothing=0; labels are int64.
-// d loss / d z_p = g * (softmax(z_p) - onehot(y_p)) / #valid  (g = upstream grad).
+// The full-resolution logits z_p are never stored: each kernel recomputes them from the NHWC low-resolution
+// logits (4 taps x C), which stay L2-resident.  Every reduction is deterministic: register accumulators, per-block
+// partials in a fixed order, then one fp64 pass; integer atomics where counts are binned (integer sums do not
+// depend on arrival order).  A label outside [0, C) that is not ignore_index (aten raises "Target out of bounds")
+// is counted in stats[2] and poisons the loss and the gradient with NaN -- stream-ordered, no host sync; the host
+// raises when it reads the loss (seg_amd.train / engine.check_targets).
 //
-// The full-resolution logits z_p are never stored: each kernel recomputes them
-// from the NHWC low-resolution logits (4 taps x C), which stay L2-resident.
-// The loss reduction is deterministic: per-block partials, then one fp64 pass.
-// A label outside [0, C) that is not ignore_index (aten raises "Target out of
-// bounds") is counted in out2[2] and poisons the loss and the gradient with NaN --
-// stream-ordered, no host sync; the host raises when it reads the loss
-// (seg_amd.train / engine.check_targets).
-//
-// The seg_cew_* entry points are the same kernels with aten's remaining options for
-// class-index targets (the instantiations that take a CeOpt): class weights w (all ones when NULL),
-// label smoothing eps and reduction mean / sum.  Over the valid pixels V,
-//   nll    = sum_p w[y_p] * (lse_p - z_p[y_p]),   smooth = sum_p sum_c w[c] * (lse_p - z_p[c]),
-//   D      = sum_p w[y_p] (mean) | 1 (sum),       loss   = ((1 - eps) * nll + (eps / C) * smooth) / D,
-//   d loss / d z_p[c] = (g / D) * [(1 - eps) * w[y_p] * (softmax_c - [c == y_p])
-//                                  + (eps / C) * (softmax_c * sum_k w[k] - w[c])].
-// Same grid, same pixel -> thread mapping and the same per-pixel expressions as the plain
-// kernels: with w = 1 (or NULL), eps = 0 and mean reduction every term is the plain kernel's
-// expression times 1 plus 0, so loss, D and gradient are bitwise the plain entry points'.
+// What is shared, each defined once in the first namespace below, and what therefore holds bit for bit by
+// construction rather than by keeping copies in step:
+//   pixel_of, full_res_logits, softmax_stats   every kernel of every family recomputes the same logits, row maximum,
+//                                              exponentials and z[y] of a pixel: eval = loss, gradient = forward;
+//   class_weights, pick                        w[y] by the select that picks z[y]; with w = 1 (or NULL), eps = 0 and
+//                                              mean reduction every weighted term is the plain term times 1 plus 0,
+//                                              so seg_cew_* without options is seg_ce_*, and so on up the families;
+//   ce_scale                                   the gradient's g / D, NaN behind an out-of-range label: the OHEM
+//                                              gradient on K is the weighted gradient;
+//   argmax_real, hist_clear / _count / _flush  validation's argmax (strict >, ascending: ties go to the lowest index,
+//                                              torch.max's rule; padded lanes never compete) and confusion matrix;
+//   block_partials, column_sums_f64            the per-block partials and the finalize's fp64 sums: out[0..2] of an
+//                                              eval call are the loss call's;
+//   zero_row, store_quad                       the gradient rows or NCHW planes, bf16 = fp32 rounded once;
+//   up_scale, loss_blocks, grad_blocks,        the host side: align-corners scales, grids, the argument checks and
+//   loss_geom_ok, rows_ok, SEG_LAUNCH_CP       the dispatch over CP = round4(C).
+// A new loss family calls these; it does not copy them.
 #include "common.h"
 
 // Every rounding in this file is written out: no implicit contraction of a * b + c into an fma,
 // and __builtin_fmaf where one is meant.  Left to the compiler, the same source expression (the
 // bilinear blend above all) was contracted differently from one instantiation to the next, so
-// the loss, eval and gradient kernels, their bf16 twins and the weighted forms recomputed logits
-// that differed in the last bit.  Now they all recompute the same numbers, and what the header
-// promises bit for bit (eval = loss, bf16 = fp32 rounded once, no options = plain) holds by
-// construction.  The forms chosen are the ones the fp32 gradient kernels always compiled to.
+// kernels that should agree recomputed logits that differed in the last bit.  The forms chosen
+// are the ones the fp32 gradient kernels always compiled to.
 #pragma clang fp contract(off)
 
 namespace {
@@ -41,6 +48,17 @@ namespace {
 // LinAC / lin_ac (common.h): the align_corners=True source index and tap weights of every kernel in this file.
 
 constexpr int CMAX = 32;
+
+// Pixel p of [N][Ho][Wo]: image, offset in its plane, row, column.
+struct Pix {
+  int n, rem, r, s;
+};
+__device__ __forceinline__ Pix pixel_of(long p, int Ho, int Wo) {
+  const int n = (int)(p / ((long)Ho * Wo));
+  const int rem = (int)(p - (long)n * Ho * Wo);
+  const int r = rem / Wo;
+  return Pix{n, rem, r, rem - r * Wo};
+}
 
 // Recompute the CP (= round4(C)) full-res logits of pixel (n, r, s); the class
 // loops are unrolled over CP so z stays in registers with constant indices.
@@ -97,9 +115,158 @@ __device__ __forceinline__ float class_weights(const float* __restrict__ cw, int
   return sw;
 }
 
-// The options of the weighted / smoothed form.  The kernels take them as a trailing parameter pack
-// that is empty for the plain entry points, whose instantiations therefore keep their parameters
-// and compile none of the option code.
+// w[y] by the select that picks z[y] in softmax_stats (0 when y is no lane of w)
+template <int CP>
+__device__ __forceinline__ float pick(const float (&w)[CP], int y) {
+  float v = 0.f;
+#pragma unroll
+  for (int c = 0; c < CP; ++c) v = c == y ? w[c] : v;
+  return v;
+}
+
+// The cross-entropy gradient's scale g / D, or NaN when the forward counted an out-of-range label (stats[2]): the
+// loss already is
+__device__ __forceinline__ float ce_scale(const float* __restrict__ stats, const float* __restrict__ gout) {
+  return stats[2] > 0.f ? __builtin_nanf("") : gout[0] / stats[1];
+}
+
+// Validation: the argmax over the C real classes (strict >, ascending; the padded lanes C..CP-1 never compete) ...
+template <int CP>
+__device__ __forceinline__ int argmax_real(const float (&z)[CP], int C) {
+  int pred = 0;
+  float best = z[0];
+#pragma unroll
+  for (int c = 1; c < CP; ++c)
+    if (c < C && z[c] > best) {
+      best = z[c];
+      pred = c;
+    }
+  return pred;
+}
+
+// ... binned into a per-block LDS histogram [label][prediction] (`__shared__ int hist[CMAX * CMAX]` in the kernel),
+// whose non-zero bins are then added to `confusion` with 64-bit integer atomics.  The caller puts a __syncthreads()
+// between clear and count and between count and flush; both are barriers the kernel has anyway.
+__device__ __forceinline__ void hist_clear(int* hist, int C) {
+  for (int i = threadIdx.x; i < C * C; i += blockDim.x) hist[i] = 0;
+}
+__device__ __forceinline__ void hist_count(int* hist, int C, int y, int pred) { atomicAdd(&hist[y * C + pred], 1); }
+__device__ __forceinline__ void hist_flush(const int* hist, int C, unsigned long long* __restrict__ confusion) {
+  for (int i = threadIdx.x; i < C * C; i += blockDim.x) {
+    const int v = hist[i];
+    if (v) atomicAdd(confusion + i, (unsigned long long)v);
+  }
+}
+
+// A 256-thread block's NP sums: the wave butterfly, lane 0 of each of the four waves through LDS, one
+// __syncthreads() -- which also closes whatever LDS counters the kernel filled before the call -- then thread j
+// writes red[0][j] + red[1][j] + red[2][j] + red[3][j] to part[at(j)] (at(j) < 0: no store).  Which thread adds the
+// four does not change the number: the same four addends in the same order.
+template <int NP, typename At>
+__device__ __forceinline__ void block_partials(const float (&v)[NP], float (&red)[4][NP], float* __restrict__ part,
+                                               At at) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int j = 0; j < NP; ++j) {
+    const float s = wave_sum(v[j]);
+    if (lane == 0) red[wave][j] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x < NP) {
+    const int j = threadIdx.x;
+    const long i = at(j);
+    if (i >= 0) part[i] = red[0][j] + red[1][j] + red[2][j] + red[3][j];
+  }
+}
+// ... in rows of NP per block, part[NP * block + j]
+template <int NP>
+__device__ __forceinline__ void block_partials(const float (&v)[NP], float (&red)[4][NP], float* __restrict__ part) {
+  block_partials<NP>(v, red, part, [](int j) { return (long)(NP * blockIdx.x + j); });
+}
+
+// The finalize's sums over the blocks, by one wave in fp64: tot[j] = sum_k part[stride * k + j], lane i taking
+// blocks i, i + 64, ..., then a 64-lane butterfly that leaves the totals in every lane.
+template <int NC>
+__device__ __forceinline__ void column_sums_f64(const float* __restrict__ part, int nblk, int stride,
+                                                double (&tot)[NC]) {
+#pragma unroll
+  for (int j = 0; j < NC; ++j) tot[j] = 0.0;
+  for (int k = threadIdx.x & 63; k < nblk; k += 64) {
+#pragma unroll
+    for (int j = 0; j < NC; ++j) tot[j] += part[stride * k + j];
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+#pragma unroll
+    for (int j = 0; j < NC; ++j) tot[j] += __shfl_xor(tot[j], o, 64);
+  }
+}
+
+// The gradient of one pixel: T rows [pixel][ldh] at d, or (NCHW) fp32 planes [N][C][Ho][Wo] with this pixel's
+// class 0 at dn.  The planes are what the bf16io twins of seg_ohem_* and seg_kd_* write: the low-resolution
+// gradient then sums unrounded terms, as it does behind the full-resolution logits of the model's forward; bf16 rows
+// would put an error of 2^-9 on every term, 2e-4 on the head's parameter gradients.
+template <int CP, bool NCHW, typename T>
+__device__ __forceinline__ void zero_row(T* d, float* dn = nullptr, int C = 0, long plane = 0) {
+  if constexpr (NCHW) {
+    for (int c = 0; c < C; ++c) dn[c * plane] = 0.f;
+  } else {
+#pragma unroll
+    for (int c = 0; c < CP; c += 4) st4(d + c, f32x4{0.f, 0.f, 0.f, 0.f});
+  }
+}
+template <bool NCHW, typename T>
+__device__ __forceinline__ void store_quad(T* d, float* dn, int c, int C, long plane, f32x4 o) {
+  if constexpr (NCHW) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (c + j < C) dn[(c + j) * plane] = o[j];
+  } else {
+    st4(d + c, o);
+  }
+}
+
+// ---- the host side ----
+struct UpScale {
+  float sh, sw;
+};
+inline UpScale up_scale(int H, int W, int Ho, int Wo) {
+  return UpScale{Ho > 1 ? (float)(H - 1) / (float)(Ho - 1) : 0.f, Wo > 1 ? (float)(W - 1) / (float)(Wo - 1) : 0.f};
+}
+
+int loss_blocks(long total) { return (int)std::min<long>(seg_cdiv(total, 256), 2048); }
+int grad_blocks(long total) { return (int)std::min<long>(seg_cdiv(total, 256), 8192); }
+
+// Low-resolution rows of ld floats hold CP = round4(C) readable ones; the gradient's rows of ldh likewise.
+inline bool loss_geom_ok(long ld, int C) { return !(ld & 3) && C >= 1 && C <= CMAX && ld >= C; }
+inline bool rows_ok(long ldh, int C) { return !(ldh & 3) && ldh >= C; }
+
+// Launch KERNEL<CP, TARGS...> with CP = round4(C) on `grid` blocks of 256: the class loops of every kernel are
+// unrolled over CP.  TARGS is the parenthesised rest of the template argument list.
+#define SEG_UNPAREN(...) __VA_ARGS__
+#define SEG_CP_CASE(CP, KERNEL, TARGS, grid, stream, ...)                                                     \
+  case CP:                                                                                                    \
+    hipLaunchKernelGGL((KERNEL<CP, SEG_UNPAREN TARGS>), dim3(grid), dim3(256), 0, stream, __VA_ARGS__);       \
+    break;
+#define SEG_LAUNCH_CP(C, KERNEL, TARGS, grid, stream, ...)          \
+  switch ((C + 3) & ~3) {                                           \
+    SEG_CP_CASE(4, KERNEL, TARGS, grid, stream, __VA_ARGS__)        \
+    SEG_CP_CASE(8, KERNEL, TARGS, grid, stream, __VA_ARGS__)        \
+    SEG_CP_CASE(12, KERNEL, TARGS, grid, stream, __VA_ARGS__)       \
+    SEG_CP_CASE(16, KERNEL, TARGS, grid, stream, __VA_ARGS__)       \
+    SEG_CP_CASE(20, KERNEL, TARGS, grid, stream, __VA_ARGS__)       \
+    SEG_CP_CASE(24, KERNEL, TARGS, grid, stream, __VA_ARGS__)       \
+    SEG_CP_CASE(28, KERNEL, TARGS, grid, stream, __VA_ARGS__)       \
+    SEG_CP_CASE(32, KERNEL, TARGS, grid, stream, __VA_ARGS__)       \
+  }
+
+// ---- seg_ce_* and, with a CeOpt, seg_cew_* ----
+// Over the valid pixels V, with class weights w (all ones when NULL), label smoothing eps, reduction mean / sum:
+//   nll    = sum_p w[y_p] * (lse_p - z_p[y_p]),   smooth = sum_p sum_c w[c] * (lse_p - z_p[c]),
+//   D      = sum_p w[y_p] (mean) | 1 (sum),       loss   = ((1 - eps) * nll + (eps / C) * smooth) / D,
+//   d loss / d z_p[c] = (g / D) * [(1 - eps) * w[y_p] * (softmax_c - [c == y_p])
+//                                  + (eps / C) * (softmax_c * sum_k w[k] - w[c])].
+// The kernels take the options as a trailing parameter pack that is empty for the plain entry points, whose
+// instantiations therefore keep their parameters and compile none of the option code.
 struct CeOpt {
   const float* cw;  // C class weights in device memory, or NULL = all ones
   float eps;        // label smoothing
@@ -108,13 +275,8 @@ struct CeOpt {
 __device__ __forceinline__ CeOpt ce_opt() { return CeOpt{nullptr, 0.f, 0}; }
 __device__ __forceinline__ CeOpt ce_opt(CeOpt o) { return o; }
 
-// EVAL: the validation form (seg_ce_upsample_eval).  On top of the loss partials -- same grid,
-// same order, so out3 is bitwise the loss kernel's -- each valid pixel's argmax over the C real
-// classes (strict >, ascending: ties go to the lowest index, torch.max's rule) is binned into a
-// per-block LDS histogram [label][prediction]; its non-zero bins are then added to `confusion`
-// with 64-bit integer atomics (integer sums do not depend on arrival order: deterministic).
-// O = CeOpt: the weighted / smoothed form (seg_cew_*).  Five partials per block instead of three:
-// [nll, sum of w[y], #out-of-range, smooth, #valid].
+// Three partials per block [nll, #valid, #out-of-range]; O = CeOpt: five, [nll, sum of w[y], #out-of-range, smooth,
+// #valid].  EVAL: the validation form, the same partials plus the confusion matrix.
 template <int CP, typename T, bool EVAL, typename... O>
 __global__ __launch_bounds__(256) void ce_up_loss_kernel(const T* __restrict__ low, long ld, int N, int H, int W,
                                                          int C, const long long* __restrict__ labels, int Ho, int Wo,
@@ -123,11 +285,10 @@ __global__ __launch_bounds__(256) void ce_up_loss_kernel(const T* __restrict__ l
                                                          unsigned long long* __restrict__ confusion, O... opt) {
   constexpr bool WS = sizeof...(O) > 0;
   constexpr int NP = WS ? 5 : 3;
-  __shared__ float red_l[4], red_c[4], red_b[4];
-  __shared__ float red_s[WS ? 4 : 1], red_v[WS ? 4 : 1];
+  __shared__ float red[4][NP];
   __shared__ int hist[EVAL ? CMAX * CMAX : 1];
   if constexpr (EVAL) {
-    for (int i = threadIdx.x; i < C * C; i += blockDim.x) hist[i] = 0;
+    hist_clear(hist, C);
     __syncthreads();
   }
   const long total = (long)N * Ho * Wo;
@@ -142,21 +303,17 @@ __global__ __launch_bounds__(256) void ce_up_loss_kernel(const T* __restrict__ l
       bad += 1.f;
       continue;
     }
-    const int n = (int)(p / ((long)Ho * Wo));
-    const int rem = (int)(p - (long)n * Ho * Wo);
-    const int r = rem / Wo, s = rem - r * Wo;
+    const Pix px = pixel_of(p, Ho, Wo);
     float z[CP];
-    full_res_logits<CP, T>(low, ld, H, W, n, r, s, sh, sw, z);
+    full_res_logits<CP, T>(low, ld, H, W, px.n, px.r, px.s, sh, sw, z);
     float m, se, zy;
     softmax_stats<CP>(z, C, (int)y, m, se, zy, false);
     if constexpr (WS) {
-      // w[y] by the select that picks z[y]; sum_c w[c] * (z[c] - m) after the row maximum is gone
-      float wy = 0.f, wz = 0.f;
+      const float wy = pick<CP>(w, (int)y);
+      float wz = 0.f;  // sum_c w[c] * (z[c] - m) after the row maximum is gone
 #pragma unroll
-      for (int c = 0; c < CP; ++c) {
-        wy = c == (int)y ? w[c] : wy;
+      for (int c = 0; c < CP; ++c)
         if (c < C) wz = __builtin_fmaf(w[c], z[c] - m, wz);  // the padded lanes may hold anything
-      }
       const float lse = logf(se);
       lsum = __builtin_fmaf(wy, m + lse - zy, lsum);  // wy = 1: the plain branch's sum
       cnt += wy;
@@ -166,59 +323,20 @@ __global__ __launch_bounds__(256) void ce_up_loss_kernel(const T* __restrict__ l
       lsum += m + logf(se) - zy;
       cnt += 1.f;
     }
-    if constexpr (EVAL) {
-      int pred = 0;
-      float best = z[0];
-#pragma unroll
-      for (int c = 1; c < CP; ++c)
-        if (c < C && z[c] > best) {  // the padded lanes C..CP-1 never compete
-          best = z[c];
-          pred = c;
-        }
-      atomicAdd(&hist[(int)y * C + pred], 1);
-    }
+    if constexpr (EVAL) hist_count(hist, C, (int)y, argmax_real<CP>(z, C));
   }
-  lsum = wave_sum(lsum);
-  cnt = wave_sum(cnt);
-  bad = wave_sum(bad);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) { red_l[wave] = lsum; red_c[wave] = cnt; red_b[wave] = bad; }
-  if constexpr (WS) {
-    ssum = wave_sum(ssum);
-    val = wave_sum(val);
-    if (lane == 0) { red_s[wave] = ssum; red_v[wave] = val; }
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    part[NP * blockIdx.x] = red_l[0] + red_l[1] + red_l[2] + red_l[3];
-    part[NP * blockIdx.x + 1] = red_c[0] + red_c[1] + red_c[2] + red_c[3];
-    part[NP * blockIdx.x + 2] = red_b[0] + red_b[1] + red_b[2] + red_b[3];
-    if constexpr (WS) {
-      part[NP * blockIdx.x + 3] = red_s[0] + red_s[1] + red_s[2] + red_s[3];
-      part[NP * blockIdx.x + 4] = red_v[0] + red_v[1] + red_v[2] + red_v[3];
-    }
-  }
-  if constexpr (EVAL) {  // the __syncthreads above also closed the histogram
-    for (int i = threadIdx.x; i < C * C; i += blockDim.x) {
-      const int v = hist[i];
-      if (v) atomicAdd(confusion + i, (unsigned long long)v);
-    }
-  }
+  float v[NP];
+  v[0] = lsum, v[1] = cnt, v[2] = bad;
+  if constexpr (WS) v[3] = ssum, v[4] = val;
+  block_partials<NP>(v, red, part);
+  if constexpr (EVAL) hist_flush(hist, C, confusion);
 }
 
 // out[0] = mean loss, out[1] = #valid pixels, out[2] = #out-of-range labels (as floats)
 __global__ void ce_finalize_kernel(const float* __restrict__ part, int nblk, float* out) {
-  double l = 0.0, c = 0.0, b = 0.0;
-  for (int k = threadIdx.x; k < nblk; k += 64) {
-    l += part[3 * k];
-    c += part[3 * k + 1];
-    b += part[3 * k + 2];
-  }
-  for (int o = 32; o > 0; o >>= 1) {
-    l += __shfl_xor(l, o, 64);
-    c += __shfl_xor(c, o, 64);
-    b += __shfl_xor(b, o, 64);
-  }
+  double t[3];
+  column_sums_f64<3>(part, nblk, 3, t);
+  const double l = t[0], c = t[1], b = t[2];
   if (threadIdx.x == 0) {
     out[0] = b > 0.0 ? __builtin_nanf("") : (float)(l / c);  // 0/0 = nan when every pixel is ignored, as aten
     out[1] = (float)c;
@@ -231,21 +349,9 @@ __global__ void ce_finalize_kernel(const float* __restrict__ part, int nblk, flo
 // the loss is then the plain finalize's l / c.
 __global__ void cew_finalize_kernel(const float* __restrict__ part, int nblk, float eps, int C, int reduction,
                                     float* out) {
-  double l = 0.0, c = 0.0, b = 0.0, sm = 0.0, v = 0.0;
-  for (int k = threadIdx.x; k < nblk; k += 64) {
-    l += part[5 * k];
-    c += part[5 * k + 1];
-    b += part[5 * k + 2];
-    sm += part[5 * k + 3];
-    v += part[5 * k + 4];
-  }
-  for (int o = 32; o > 0; o >>= 1) {
-    l += __shfl_xor(l, o, 64);
-    c += __shfl_xor(c, o, 64);
-    b += __shfl_xor(b, o, 64);
-    sm += __shfl_xor(sm, o, 64);
-    v += __shfl_xor(v, o, 64);
-  }
+  double t[5];
+  column_sums_f64<5>(part, nblk, 5, t);
+  const double l = t[0], c = t[1], b = t[2], sm = t[3], v = t[4];
   if (threadIdx.x == 0) {
     const double d = reduction == 0 ? c : 1.0;
     const double num = eps > 0.f ? (1.0 - (double)eps) * l + ((double)eps / C) * sm : l;
@@ -256,8 +362,7 @@ __global__ void cew_finalize_kernel(const float* __restrict__ part, int nblk, fl
   }
 }
 
-// dhigh[p][c] = g * (softmax(z_p)[c] - [c == y_p]) / count, NHWC (ld >= round4(C)).
-// O = CeOpt: g / D * [(1 - eps) * w[y] * (softmax_c - [c == y]) + (eps / C) * (softmax_c * sum w - w[c])], D = stats[1].
+// dhigh[p][c] = g * (softmax(z_p)[c] - [c == y_p]) / count, NHWC rows; O = CeOpt: the weighted form, D = stats[1].
 template <int CP, typename T, typename... O>
 __global__ __launch_bounds__(256) void ce_up_grad_kernel(const T* __restrict__ low, long ld, int N, int H, int W,
                                                          int C, const long long* __restrict__ labels, int Ho, int Wo,
@@ -266,7 +371,7 @@ __global__ __launch_bounds__(256) void ce_up_grad_kernel(const T* __restrict__ l
                                                          T* __restrict__ dhigh, long ldh, O... opt) {
   constexpr bool WS = sizeof...(O) > 0;
   const long total = (long)N * Ho * Wo;
-  const float scale = stats[2] > 0.f ? __builtin_nanf("") : gout[0] / stats[1];
+  const float scale = ce_scale(stats, gout);
   float w[WS ? CP : 1];
   float wsum = 0.f, keep = 1.f, spread = 0.f;
   if constexpr (WS) {
@@ -278,38 +383,31 @@ __global__ __launch_bounds__(256) void ce_up_grad_kernel(const T* __restrict__ l
   for (long p = blockIdx.x * (long)blockDim.x + threadIdx.x; p < total; p += (long)gridDim.x * blockDim.x) {
     const long long y = labels[p];
     T* d = dhigh + p * ldh;
-    if (y == ignore_index || y < 0 || y >= C) {  // out of range: scale is NaN, the loss already is
-#pragma unroll
-      for (int c = 0; c < CP; c += 4) st4(d + c, f32x4{0.f, 0.f, 0.f, 0.f});
+    if (y == ignore_index || y < 0 || y >= C) {
+      zero_row<CP, false>(d);
       continue;
     }
-    const int n = (int)(p / ((long)Ho * Wo));
-    const int rem = (int)(p - (long)n * Ho * Wo);
-    const int r = rem / Wo, s = rem - r * Wo;
+    const Pix px = pixel_of(p, Ho, Wo);
     float z[CP];
-    full_res_logits<CP, T>(low, ld, H, W, n, r, s, sh, sw, z);
+    full_res_logits<CP, T>(low, ld, H, W, px.n, px.r, px.s, sh, sw, z);
     float m, se, zy;
     softmax_stats<CP>(z, C, (int)y, m, se, zy, true);
     const float inv = 1.f / se;
     float kw = 0.f;  // (1 - eps) * w[y]
-    if constexpr (WS) {
-#pragma unroll
-      for (int c = 0; c < CP; ++c) kw = c == (int)y ? w[c] : kw;
-      kw *= keep;
-    }
+    if constexpr (WS) kw = pick<CP>(w, (int)y) * keep;
 #pragma unroll
     for (int c = 0; c < CP; c += 4) {
       f32x4 o;
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const int cc = c + j;
+        const float nl = __builtin_fmaf(z[cc], inv, cc == (int)y ? -1.f : -0.f);
         if constexpr (WS) {
-          // softmax - onehot as in the plain branch: with w = 1 and eps = 0 the rest is * 1 and + 0
-          const float nl = __builtin_fmaf(z[cc], inv, cc == (int)y ? -1.f : -0.f);
+          // with w = 1 and eps = 0 the rest is * 1 and + 0
           const float sm = __builtin_fmaf(z[cc] * inv, wsum, -w[cc]);
           o[j] = cc < C ? scale * __builtin_fmaf(spread, sm, kw * nl) : 0.f;
         } else {
-          o[j] = cc < C ? scale * __builtin_fmaf(z[cc], inv, cc == (int)y ? -1.f : -0.f) : 0.f;
+          o[j] = cc < C ? scale * nl : 0.f;
         }
       }
       st4(d + c, o);
@@ -317,39 +415,24 @@ __global__ __launch_bounds__(256) void ce_up_grad_kernel(const T* __restrict__ l
   }
 }
 
-int loss_blocks(long total) { return (int)std::min<long>(seg_cdiv(total, 256), 2048); }
-
 }  // namespace
 
 SEG_API long seg_ce_workspace_floats(long pixels) { return 3L * loss_blocks(pixels); }
 
-// Mean CE of bilinear_ac_true_x(Ho,Wo)(low) against labels.  out3[0] = loss,
-// out3[1] = number of non-ignored pixels, out3[2] = number of out-of-range labels.  `work` >= seg_ce_workspace_floats(N*Ho*Wo).
-// EVAL: also add each valid pixel to confusion[label][argmax] (C*C int64, device memory).
-// opt (seg_cew_*): one CeOpt; out2 is then out4.
 inline bool ce_opt_ok() { return true; }
 inline bool ce_opt_ok(CeOpt o) { return (o.reduction == 0 || o.reduction == 1) && o.eps >= 0.f && o.eps <= 1.f; }
 
+// opt (seg_cew_*): one CeOpt; out2 is then out4.
 template <typename T, bool EVAL = false, typename... O>
 static int ce_loss_impl(const T* low, long ld, int N, int H, int W, int C, const long long* labels, int Ho, int Wo,
                         int ignore_index, float* work, float* out2, hipStream_t stream, long long* confusion,
                         O... opt) {
   constexpr bool WS = sizeof...(O) > 0;
-  if ((ld & 3) || C > CMAX || C < 1 || (EVAL && !confusion) || !ce_opt_ok(opt...)) return (int)hipErrorInvalidValue;
-  const long total = (long)N * Ho * Wo;
-  const int nb = loss_blocks(total);
-  const float sh = Ho > 1 ? (float)(H - 1) / (float)(Ho - 1) : 0.f;
-  const float sw = Wo > 1 ? (float)(W - 1) / (float)(Wo - 1) : 0.f;
-#define SEG_CE_L(CP)                                                                                          \
-  case CP:                                                                                                    \
-    hipLaunchKernelGGL((ce_up_loss_kernel<CP, T, EVAL, O...>), dim3(nb), dim3(256), 0, stream, low, ld, N, H,  \
-                       W, C, labels, Ho, Wo, sh, sw, ignore_index, work, (unsigned long long*)confusion,     \
-                       opt...);                                                                               \
-    break
-  switch ((C + 3) & ~3) {
-    SEG_CE_L(4); SEG_CE_L(8); SEG_CE_L(12); SEG_CE_L(16); SEG_CE_L(20); SEG_CE_L(24); SEG_CE_L(28); SEG_CE_L(32);
-  }
-#undef SEG_CE_L
+  if (!loss_geom_ok(ld, C) || (EVAL && !confusion) || !ce_opt_ok(opt...)) return (int)hipErrorInvalidValue;
+  const int nb = loss_blocks((long)N * Ho * Wo);
+  const UpScale up = up_scale(H, W, Ho, Wo);
+  SEG_LAUNCH_CP(C, ce_up_loss_kernel, (T, EVAL, O...), nb, stream, low, ld, N, H, W, C, labels, Ho, Wo, up.sh, up.sw,
+                ignore_index, work, (unsigned long long*)confusion, opt...)
   if constexpr (WS) {
     const CeOpt o = CeOpt{opt...};
     hipLaunchKernelGGL(cew_finalize_kernel, dim3(1), dim3(64), 0, stream, work, nb, o.eps, C, o.reduction, out2);
@@ -357,6 +440,9 @@ static int ce_loss_impl(const T* low, long ld, int N, int H, int W, int C, const
     hipLaunchKernelGGL(ce_finalize_kernel, dim3(1), dim3(64), 0, stream, work, nb, out2);
   SEG_RET_LAST();
 }
+
+// Mean CE of bilinear_ac_true_x(Ho,Wo)(low) against labels.  out3[0] = loss, out3[1] = number of non-ignored
+// pixels, out3[2] = number of out-of-range labels.  `work` >= seg_ce_workspace_floats(N*Ho*Wo).
 SEG_API int seg_ce_upsample_loss(const float* low, long ld, int N, int H, int W, int C, const long long* labels, int Ho,
                                  int Wo, int ignore_index, float* work, float* out2, hipStream_t stream) {
   return ce_loss_impl(low, ld, N, H, W, C, labels, Ho, Wo, ignore_index, work, out2, stream, nullptr);
@@ -367,8 +453,8 @@ SEG_API int seg_ce_upsample_loss_bf16io(const __bf16* low, long ld, int N, int H
   return ce_loss_impl(low, ld, N, H, W, C, labels, Ho, Wo, ignore_index, work, out2, stream, nullptr);
 }
 
-// Validation: seg_ce_upsample_loss (out3 bitwise the same) plus the confusion matrix of the
-// full-resolution argmax, confusion[label * C + prediction] += 1 per non-ignored in-range pixel.
+// Validation: seg_ce_upsample_loss plus the confusion matrix of the full-resolution argmax,
+// confusion[label * C + prediction] += 1 per non-ignored in-range pixel (C*C int64, device memory).
 SEG_API int seg_ce_upsample_eval(const float* low, long ld, int N, int H, int W, int C, const long long* labels, int Ho,
                                  int Wo, int ignore_index, float* work, float* out3, long long* confusion,
                                  hipStream_t stream) {
@@ -380,26 +466,16 @@ SEG_API int seg_ce_upsample_eval_bf16io(const __bf16* low, long ld, int N, int H
   return ce_loss_impl<__bf16, true>(low, ld, N, H, W, C, labels, Ho, Wo, ignore_index, work, out3, stream, confusion);
 }
 
-// Full-resolution logit gradient (NHWC, ldh >= round4(C)); follow with
-// seg_upsample_bwd(nchw_grad = 0, ac = 1) to reach the low-res logits.
+// Full-resolution logit gradient (NHWC rows of ldh); follow with seg_upsample_bwd(nchw_grad = 0, ac = 1) to reach
+// the low-res logits.
 template <typename T, typename... O>
 static int ce_grad_impl(const T* low, long ld, int N, int H, int W, int C, const long long* labels, int Ho, int Wo,
                         int ignore_index, const float* grad_out, const float* stats, T* dhigh, long ldh,
                         hipStream_t stream, O... opt) {
-  if ((ld & 3) || (ldh & 3) || C > CMAX || C < 1 || !ce_opt_ok(opt...)) return (int)hipErrorInvalidValue;
-  const long total = (long)N * Ho * Wo;
-  const float sh = Ho > 1 ? (float)(H - 1) / (float)(Ho - 1) : 0.f;
-  const float sw = Wo > 1 ? (float)(W - 1) / (float)(Wo - 1) : 0.f;
-  const int grid = (int)std::min<long>(seg_cdiv(total, 256), 8192);
-#define SEG_CE_G(CP)                                                                                            \
-  case CP:                                                                                                      \
-    hipLaunchKernelGGL((ce_up_grad_kernel<CP, T, O...>), dim3(grid), dim3(256), 0, stream, low, ld, N, H, W, C,  \
-                       labels, Ho, Wo, sh, sw, ignore_index, grad_out, stats, dhigh, ldh, opt...);             \
-    break
-  switch ((C + 3) & ~3) {
-    SEG_CE_G(4); SEG_CE_G(8); SEG_CE_G(12); SEG_CE_G(16); SEG_CE_G(20); SEG_CE_G(24); SEG_CE_G(28); SEG_CE_G(32);
-  }
-#undef SEG_CE_G
+  if (!loss_geom_ok(ld, C) || !rows_ok(ldh, C) || !ce_opt_ok(opt...)) return (int)hipErrorInvalidValue;
+  const UpScale up = up_scale(H, W, Ho, Wo);
+  SEG_LAUNCH_CP(C, ce_up_grad_kernel, (T, O...), grad_blocks((long)N * Ho * Wo), stream, low, ld, N, H, W, C, labels,
+                Ho, Wo, up.sh, up.sw, ignore_index, grad_out, stats, dhigh, ldh, opt...)
   SEG_RET_LAST();
 }
 SEG_API int seg_ce_upsample_grad(const float* low, long ld, int N, int H, int W, int C, const long long* labels, int Ho,
@@ -414,7 +490,6 @@ SEG_API int seg_ce_upsample_grad_bf16io(const __bf16* low, long ld, int N, int H
   return ce_grad_impl(low, ld, N, H, W, C, labels, Ho, Wo, ignore_index, grad_out, stats, dhigh, ldh, stream);
 }
 
-// ---- class weights, label smoothing, reduction mean / sum (the header comment has the formulas) ----
 // out4 = [loss, D, #out-of-range labels, #valid pixels]; `work` >= seg_cew_workspace_floats(N*Ho*Wo).
 SEG_API long seg_cew_workspace_floats(long pixels) { return 5L * loss_blocks(pixels); }
 
@@ -467,10 +542,9 @@ SEG_API int seg_cew_upsample_grad_bf16io(const __bf16* low, long ld, int N, int 
 //   Dice = sum_c m_c (1 - (2 I_c + smooth) / U_c) / max(M, 1),  m_c = [T_c > 0],  M = sum_c m_c,
 //   loss = ce F + dice Dice    (a term whose coefficient is 0 is left out, so its 0/0 never reaches the loss).
 // One pass over the pixels writes, per block, the five partials of the seg_cew_* kernels, the focal sum and I_c, S_c,
-// T_c: register accumulators, the wave butterfly, the four waves through LDS in a fixed order -- no float atomics,
-// so two calls agree bitwise (T_c is an LDS integer count: exact).  The partials lie column-major, part[col * nblk +
-// block], so that the one-block fp64 finalize reads them coalesced; it writes stats = [loss, D, #out-of-range
-// labels, #valid, F, Dice] and the table of the Dice gradient's per-class coefficients
+// T_c (T_c is an LDS integer count: exact).  The partials lie column-major, part[col * nblk + block], so that the
+// one-block fp64 finalize reads them coalesced; it writes stats = [loss, D, #out-of-range labels, #valid, F, Dice]
+// and the table of the Dice gradient's per-class coefficients
 //   a_c = m_c 2 / (M U_c)  at table[c],   b_c = m_c (2 I_c + smooth) / (M U_c^2)  at table[32 + c]
 // (d Dice / d s_p[c] = q_c = b_c - a_c [c = y_p]).  The gradient kernel reads them as wave-uniform values, like the
 // class weights:
@@ -510,8 +584,7 @@ __global__ __launch_bounds__(256) void sl_up_loss_kernel(const T* __restrict__ l
   __shared__ int tcnt[CP];
   __shared__ int hist[EVAL ? CMAX * CMAX : 1];
   if (threadIdx.x < CP) tcnt[threadIdx.x] = 0;
-  if constexpr (EVAL)
-    for (int i = threadIdx.x; i < C * C; i += blockDim.x) hist[i] = 0;
+  if constexpr (EVAL) hist_clear(hist, C);
   __syncthreads();
   const long total = (long)N * Ho * Wo;
   float lsum = 0.f, cnt = 0.f, bad = 0.f, ssum = 0.f, val = 0.f, fsum = 0.f;
@@ -528,21 +601,19 @@ __global__ __launch_bounds__(256) void sl_up_loss_kernel(const T* __restrict__ l
       bad += 1.f;
       continue;
     }
-    const int n = (int)(p / ((long)Ho * Wo));
-    const int rem = (int)(p - (long)n * Ho * Wo);
-    const int r = rem / Wo, s = rem - r * Wo;
+    const Pix px = pixel_of(p, Ho, Wo);
     float z[CP];
-    full_res_logits<CP, T>(low, ld, H, W, n, r, s, sh, sw, z);
+    full_res_logits<CP, T>(low, ld, H, W, px.n, px.r, px.s, sh, sw, z);
     float m, se, zy;
     softmax_stats<CP>(z, C, (int)y, m, se, zy, false);
     const float inv = 1.f / se;
-    float wy = 0.f, wz = 0.f, rest = 0.f;
+    const float wy = pick<CP>(w, (int)y);
+    float wz = 0.f, rest = 0.f;
 #pragma unroll
     for (int c = 0; c < CP; ++c) {
       const bool lab = c == (int)y;
       const float d = z[c] - m;
       const float e = c < C ? expf(d) : 0.f;  // the padded lanes may hold anything
-      wy = lab ? w[c] : wy;
       rest += lab ? 0.f : e;                  // sum_{c != y} e_c
       if (c < C) wz = __builtin_fmaf(w[c], d, wz);
       const float sc = e * inv;
@@ -561,17 +632,7 @@ __global__ __launch_bounds__(256) void sl_up_loss_kernel(const T* __restrict__ l
       fsum = __builtin_fmaf(wy * pw, nlp, fsum);
     }
     atomicAdd(&tcnt[(int)y], 1);
-    if constexpr (EVAL) {
-      int pred = 0;
-      float best = z[0];
-#pragma unroll
-      for (int c = 1; c < CP; ++c)
-        if (c < C && z[c] > best) {  // the padded lanes C..CP-1 never compete
-          best = z[c];
-          pred = c;
-        }
-      atomicAdd(&hist[(int)y * C + pred], 1);
-    }
+    if constexpr (EVAL) hist_count(hist, C, (int)y, argmax_real<CP>(z, C));
   }
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   lsum = wave_sum(lsum);
@@ -602,16 +663,11 @@ __global__ __launch_bounds__(256) void sl_up_loss_kernel(const T* __restrict__ l
       part[(long)(j - CP + C) * nb + blockIdx.x] = v;                // S_c: column 6 + C + c
   }
   if (threadIdx.x < C) part[(long)(SL_FIXED + 2 * C + threadIdx.x) * nb + blockIdx.x] = (float)tcnt[threadIdx.x];
-  if constexpr (EVAL) {
-    for (int i = threadIdx.x; i < C * C; i += blockDim.x) {
-      const int v = hist[i];
-      if (v) atomicAdd(confusion + i, (unsigned long long)v);
-    }
-  }
+  if constexpr (EVAL) hist_flush(hist, C, confusion);
 }
 
-// One block, four waves: each wave sums whole columns of the partials in fp64 (lane k takes blocks k, k + 64, ...,
-// then the butterfly), thread 0 forms the stats and the coefficient table from the 6 + 3 C totals.
+// One block, four waves: each wave sums whole columns of the partials in fp64, thread 0 forms the stats and the
+// coefficient table from the 6 + 3 C totals.
 __global__ __launch_bounds__(256) void sl_finalize_kernel(const float* __restrict__ part, int nblk, int C, float eps,
                                                           float ce, float dice, float gamma, float smooth,
                                                           float* __restrict__ out, float* __restrict__ table) {
@@ -619,10 +675,9 @@ __global__ __launch_bounds__(256) void sl_finalize_kernel(const float* __restric
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int ncol = SL_FIXED + 3 * C;
   for (int col = wave; col < ncol; col += 4) {
-    double a = 0.0;
-    for (int k = lane; k < nblk; k += 64) a += part[(long)col * nblk + k];
-    for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
-    if (lane == 0) tot[col] = a;
+    double a[1];
+    column_sums_f64<1>(part + (long)col * nblk, nblk, 1, a);
+    if (lane == 0) tot[col] = a[0];
   }
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -679,25 +734,21 @@ __global__ __launch_bounds__(256) void sl_up_grad_kernel(const T* __restrict__ l
   for (long p = blockIdx.x * (long)blockDim.x + threadIdx.x; p < total; p += (long)gridDim.x * blockDim.x) {
     const long long y = labels[p];
     T* d = dhigh + p * ldh;
-    if (y == ignore_index || y < 0 || y >= C) {  // out of range: the scales are NaN, the loss already is
-#pragma unroll
-      for (int c = 0; c < CP; c += 4) st4(d + c, f32x4{0.f, 0.f, 0.f, 0.f});
+    if (y == ignore_index || y < 0 || y >= C) {
+      zero_row<CP, false>(d);
       continue;
     }
-    const int n = (int)(p / ((long)Ho * Wo));
-    const int rem = (int)(p - (long)n * Ho * Wo);
-    const int r = rem / Wo, s = rem - r * Wo;
+    const Pix px = pixel_of(p, Ho, Wo);
     float z[CP];
-    full_res_logits<CP, T>(low, ld, H, W, n, r, s, sh, sw, z);
+    full_res_logits<CP, T>(low, ld, H, W, px.n, px.r, px.s, sh, sw, z);
     float m, se, zy;
     softmax_stats<CP>(z, C, (int)y, m, se, zy, true);  // z[c] = e_c now
     const float inv = 1.f / se;
-    float wy = 0.f, ey = 0.f, rest = 0.f, ay = 0.f, sb = 0.f;
+    const float wy = pick<CP>(w, (int)y), ey = pick<CP>(z, (int)y);
+    float rest = 0.f, ay = 0.f, sb = 0.f;
 #pragma unroll
     for (int c = 0; c < CP; ++c) {
       const bool lab = c == (int)y;
-      wy = lab ? w[c] : wy;
-      ey = lab ? z[c] : ey;
       rest += lab ? 0.f : z[c];
       if (has_dice) {
         ay = lab ? table[c] : ay;
@@ -737,21 +788,11 @@ template <typename T, bool EVAL>
 int sl_loss_impl(const T* low, long ld, int N, int H, int W, int C, const long long* labels, int Ho, int Wo,
                  int ignore_index, SlOpt o, float* work, float* out6, float* table, long long* confusion,
                  hipStream_t stream) {
-  if ((ld & 3) || C > CMAX || C < 1 || ld < C || (EVAL && !confusion) || !sl_opt_ok(o))
-    return (int)hipErrorInvalidValue;
-  const long total = (long)N * Ho * Wo;
-  const int nb = loss_blocks(total);
-  const float sh = Ho > 1 ? (float)(H - 1) / (float)(Ho - 1) : 0.f;
-  const float sw = Wo > 1 ? (float)(W - 1) / (float)(Wo - 1) : 0.f;
-#define SEG_SL_L(CP)                                                                                        \
-  case CP:                                                                                                  \
-    hipLaunchKernelGGL((sl_up_loss_kernel<CP, T, EVAL>), dim3(nb), dim3(256), 0, stream, low, ld, N, H, W,   \
-                       C, labels, Ho, Wo, sh, sw, ignore_index, work, (unsigned long long*)confusion, o);   \
-    break
-  switch ((C + 3) & ~3) {
-    SEG_SL_L(4); SEG_SL_L(8); SEG_SL_L(12); SEG_SL_L(16); SEG_SL_L(20); SEG_SL_L(24); SEG_SL_L(28); SEG_SL_L(32);
-  }
-#undef SEG_SL_L
+  if (!loss_geom_ok(ld, C) || (EVAL && !confusion) || !sl_opt_ok(o)) return (int)hipErrorInvalidValue;
+  const int nb = loss_blocks((long)N * Ho * Wo);
+  const UpScale up = up_scale(H, W, Ho, Wo);
+  SEG_LAUNCH_CP(C, sl_up_loss_kernel, (T, EVAL), nb, stream, low, ld, N, H, W, C, labels, Ho, Wo, up.sh, up.sw,
+                ignore_index, work, (unsigned long long*)confusion, o)
   hipLaunchKernelGGL(sl_finalize_kernel, dim3(1), dim3(256), 0, stream, work, nb, C, o.eps, o.ce, o.dice, o.gamma,
                      o.smooth, out6, table);
   SEG_RET_LAST();
@@ -761,21 +802,10 @@ template <typename T>
 int sl_grad_impl(const T* low, long ld, int N, int H, int W, int C, const long long* labels, int Ho, int Wo,
                  int ignore_index, SlOpt o, const float* grad_out, const float* stats, const float* table, T* dhigh,
                  long ldh, hipStream_t stream) {
-  if ((ld & 3) || (ldh & 3) || C > CMAX || C < 1 || ld < C || ldh < C || !sl_opt_ok(o))
-    return (int)hipErrorInvalidValue;
-  const long total = (long)N * Ho * Wo;
-  const float sh = Ho > 1 ? (float)(H - 1) / (float)(Ho - 1) : 0.f;
-  const float sw = Wo > 1 ? (float)(W - 1) / (float)(Wo - 1) : 0.f;
-  const int grid = (int)std::min<long>(seg_cdiv(total, 256), 8192);
-#define SEG_SL_G(CP)                                                                                          \
-  case CP:                                                                                                    \
-    hipLaunchKernelGGL((sl_up_grad_kernel<CP, T>), dim3(grid), dim3(256), 0, stream, low, ld, N, H, W, C,      \
-                       labels, Ho, Wo, sh, sw, ignore_index, grad_out, stats, table, dhigh, ldh, o);          \
-    break
-  switch ((C + 3) & ~3) {
-    SEG_SL_G(4); SEG_SL_G(8); SEG_SL_G(12); SEG_SL_G(16); SEG_SL_G(20); SEG_SL_G(24); SEG_SL_G(28); SEG_SL_G(32);
-  }
-#undef SEG_SL_G
+  if (!loss_geom_ok(ld, C) || !rows_ok(ldh, C) || !sl_opt_ok(o)) return (int)hipErrorInvalidValue;
+  const UpScale up = up_scale(H, W, Ho, Wo);
+  SEG_LAUNCH_CP(C, sl_up_grad_kernel, (T), grad_blocks((long)N * Ho * Wo), stream, low, ld, N, H, W, C, labels, Ho,
+                Wo, up.sh, up.sw, ignore_index, grad_out, stats, table, dhigh, ldh, o)
   SEG_RET_LAST();
 }
 
@@ -846,17 +876,16 @@ SEG_API int seg_sl_upsample_grad_bf16io(const __bf16* low, long ld, int N, int H
 // order of the values, and lambda is found exactly by a radix select over three digits of 11 / 10 / 10 bits:
 //   1. the loss pass stores l_p (4 B per pixel, -1 for an ignored or out-of-range label) at the front of `work`,
 //      counts #valid, #out-of-range and #{l_p > tau}, and histograms the top digit (per-block LDS histogram, its
-//      non-zero bins added to the global one: integer atomics only, so the sums do not depend on arrival order);
+//      non-zero bins added to the global one);
 //   2. two refine passes over the 4 B per pixel: every block finds the bin of the k-th largest in the last
 //      histogram for itself (one scan of <= 2048 counters from L2, the same result in every block; block 0 leaves it
 //      in `work` for the next launch) and histograms the next digit of the pixels in that bin.  When #{l_p > tau}
 //      already reaches k, K = {l_p > tau} and lambda is not needed: both passes return at once (the launch
 //      sequence is fixed, the tape replays it);
 //   3. the reduce pass picks the last digit -- lambda is exact -- and sums w[y] l and w[y] over K into per-block
-//      partials in a fixed order; one fp64 finalize writes stats = [loss, D, #out-of-range, #valid, #kept, cut],
-//      cut = min(tau, lambda).
-// The gradient kernel has the plain one's grid and expressions and reads the keep decision from the stored l_p, tau
-// and lambda (in `work`; +inf in threshold mode), so forward and backward agree on K by construction.
+//      partials; one fp64 finalize writes stats = [loss, D, #out-of-range, #valid, #kept, cut], cut = min(tau, lambda).
+// The gradient kernel reads the keep decision from the stored l_p, tau and lambda (in `work`; +inf in threshold
+// mode), so forward and backward agree on K by construction.
 // work: [pixels] l_p | OH_CTL words of histograms and counters (cleared on the stream by every call) | 2 floats per block.
 namespace {
 
@@ -927,8 +956,7 @@ __global__ __launch_bounds__(256) void oh_up_loss_kernel(const T* __restrict__ l
   __shared__ int hist[EVAL ? CMAX * CMAX : 1];
   for (int i = threadIdx.x; i < OH_B0; i += blockDim.x) h0[i] = 0;
   if (threadIdx.x < 3) cnt[threadIdx.x] = 0;
-  if constexpr (EVAL)
-    for (int i = threadIdx.x; i < C * C; i += blockDim.x) hist[i] = 0;
+  if constexpr (EVAL) hist_clear(hist, C);
   __syncthreads();
   const long total = (long)N * Ho * Wo;
   unsigned nvalid = 0, nbad = 0, nabove = 0;
@@ -939,11 +967,9 @@ __global__ __launch_bounds__(256) void oh_up_loss_kernel(const T* __restrict__ l
       lbuf[p] = -1.f;
       continue;
     }
-    const int n = (int)(p / ((long)Ho * Wo));
-    const int rem = (int)(p - (long)n * Ho * Wo);
-    const int r = rem / Wo, s = rem - r * Wo;
+    const Pix px = pixel_of(p, Ho, Wo);
     float z[CP];
-    full_res_logits<CP, T>(low, ld, H, W, n, r, s, sh, sw, z);
+    full_res_logits<CP, T>(low, ld, H, W, px.n, px.r, px.s, sh, sw, z);
     float m, se, zy;
     softmax_stats<CP>(z, C, (int)y, m, se, zy, false);
     const float l = m + logf(se) - zy;  // the plain kernel's per-pixel term
@@ -951,16 +977,16 @@ __global__ __launch_bounds__(256) void oh_up_loss_kernel(const T* __restrict__ l
     nvalid += 1u;
     nabove += l > tau ? 1u : 0u;
     atomicAdd(&h0[oh_key(l) >> 20], 1u);
-    if constexpr (EVAL) {
+    if constexpr (EVAL) {  // argmax_real's text: through the call, two bf16 instantiations lose a wave of occupancy
       int pred = 0;
       float best = z[0];
 #pragma unroll
       for (int c = 1; c < CP; ++c)
-        if (c < C && z[c] > best) {  // the padded lanes C..CP-1 never compete
+        if (c < C && z[c] > best) {
           best = z[c];
           pred = c;
         }
-      atomicAdd(&hist[(int)y * C + pred], 1);
+      hist_count(hist, C, (int)y, pred);
     }
   }
   if (nvalid) atomicAdd(&cnt[0], nvalid);
@@ -972,12 +998,7 @@ __global__ __launch_bounds__(256) void oh_up_loss_kernel(const T* __restrict__ l
     if (v) atomicAdd(ctl + i, v);
   }
   if (threadIdx.x < 3 && cnt[threadIdx.x]) atomicAdd(ctl + OH_CNT + threadIdx.x, cnt[threadIdx.x]);
-  if constexpr (EVAL) {
-    for (int i = threadIdx.x; i < C * C; i += blockDim.x) {
-      const int v = hist[i];
-      if (v) atomicAdd(confusion + i, (unsigned long long)v);
-    }
-  }
+  if constexpr (EVAL) hist_flush(hist, C, confusion);
 }
 
 // LEVEL 1: pick the top digit's bin from the loss pass's histogram, histogram the middle digit of its pixels.
@@ -1022,7 +1043,7 @@ __global__ __launch_bounds__(256) void oh_reduce_kernel(const float* __restrict_
                                                         long min_kept, float tau, const float* __restrict__ cw,
                                                         unsigned* __restrict__ ctl, float* __restrict__ part) {
   __shared__ unsigned s[6];
-  __shared__ float red_l[4], red_d[4];
+  __shared__ float red[4][2];
   __shared__ unsigned kept;
   unsigned* cnt = ctl + OH_CNT;
   unsigned k, lbits = OH_INF;
@@ -1044,15 +1065,10 @@ __global__ __launch_bounds__(256) void oh_reduce_kernel(const float* __restrict_
     dsum += wy;
     nk += 1u;
   }
-  lsum = wave_sum(lsum);
-  dsum = wave_sum(dsum);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) { red_l[wave] = lsum; red_d[wave] = dsum; }
   if (nk) atomicAdd(&kept, nk);
-  __syncthreads();
+  const float v[2] = {lsum, dsum};
+  block_partials<2>(v, red, part);  // its barrier also closes `kept`
   if (threadIdx.x == 0) {
-    part[2 * blockIdx.x] = red_l[0] + red_l[1] + red_l[2] + red_l[3];
-    part[2 * blockIdx.x + 1] = red_d[0] + red_d[1] + red_d[2] + red_d[3];
     if (kept) atomicAdd(cnt + OH_KEPT, kept);
     if (blockIdx.x == 0) cnt[OH_LAMBDA] = lbits;
   }
@@ -1061,15 +1077,9 @@ __global__ __launch_bounds__(256) void oh_reduce_kernel(const float* __restrict_
 // out6 = [loss, D, #out-of-range labels, #valid, #kept, cut = min(tau, lambda)]
 __global__ void oh_finalize_kernel(const float* __restrict__ part, int nblk, float tau,
                                    const unsigned* __restrict__ ctl, float* out) {
-  double l = 0.0, d = 0.0;
-  for (int k = threadIdx.x; k < nblk; k += 64) {
-    l += part[2 * k];
-    d += part[2 * k + 1];
-  }
-  for (int o = 32; o > 0; o >>= 1) {
-    l += __shfl_xor(l, o, 64);
-    d += __shfl_xor(d, o, 64);
-  }
+  double t[2];
+  column_sums_f64<2>(part, nblk, 2, t);
+  const double l = t[0], d = t[1];
   if (threadIdx.x == 0) {
     const unsigned* cnt = ctl + OH_CNT;
     out[0] = cnt[OH_BAD] > 0 ? __builtin_nanf("") : (float)(l / d);  // 0/0 = nan when nothing is kept, as aten
@@ -1083,10 +1093,7 @@ __global__ void oh_finalize_kernel(const float* __restrict__ part, int nblk, flo
 
 // dhigh[p][c] = g w[y_p] (softmax(z_p)[c] - [c == y_p]) / D on K (read from the stored l_p), zeros elsewhere: the
 // weighted gradient kernel's expression, scale * (w[y] * (softmax - onehot)), so on K the rows are what
-// seg_cew_upsample_grad writes for the labels with every pixel outside K ignored.
-// NCHW (the bf16io twin): dhigh is fp32 [N][C][Ho][Wo] instead of T rows.  The low-resolution gradient then sums
-// unrounded terms, as it does behind the full-resolution logits of the model's forward; bf16 rows would put an error
-// of 2^-9 on every term, 2e-4 on the head's parameter gradients.
+// seg_cew_upsample_grad writes for the labels with every pixel outside K ignored.  NCHW: the bf16io twin (store_quad).
 template <int CP, typename T, bool NCHW>
 __global__ __launch_bounds__(256) void oh_up_grad_kernel(const T* __restrict__ low, long ld, int N, int H, int W,
                                                          int C, const long long* __restrict__ labels, int Ho, int Wo,
@@ -1098,35 +1105,26 @@ __global__ __launch_bounds__(256) void oh_up_grad_kernel(const T* __restrict__ l
                                                          long ldh) {
   const long total = (long)N * Ho * Wo;
   const long plane = (long)Ho * Wo;
-  const float scale = stats[2] > 0.f ? __builtin_nanf("") : gout[0] / stats[1];
+  const float scale = ce_scale(stats, gout);
   const float lambda = __uint_as_float(ctl[OH_CNT + OH_LAMBDA]);
   float w[CP];
   class_weights<CP>(cw, C, w);
   for (long p = blockIdx.x * (long)blockDim.x + threadIdx.x; p < total; p += (long)gridDim.x * blockDim.x) {
     const float l = lbuf[p];
-    const int n = (int)(p / plane);
-    const int rem = (int)(p - (long)n * plane);
-    T* d = static_cast<T*>(dout) + p * ldh;                            // rows (!NCHW)
-    float* dn = static_cast<float*>(dout) + (long)n * C * plane + rem;  // class 0 of this pixel (NCHW)
-    if (!oh_valid(l) || !oh_keep(l, tau, lambda)) {  // out of range: scale is NaN, the loss already is
-      if constexpr (NCHW) {
-        for (int c = 0; c < C; ++c) dn[c * plane] = 0.f;
-      } else {
-#pragma unroll
-        for (int c = 0; c < CP; c += 4) st4(d + c, f32x4{0.f, 0.f, 0.f, 0.f});
-      }
+    const Pix px = pixel_of(p, Ho, Wo);
+    T* d = static_cast<T*>(dout) + p * ldh;
+    float* dn = static_cast<float*>(dout) + (long)px.n * C * plane + px.rem;
+    if (!oh_valid(l) || !oh_keep(l, tau, lambda)) {
+      zero_row<CP, NCHW>(d, dn, C, plane);
       continue;
     }
     const int y = (int)labels[p];
-    const int r = rem / Wo, s = rem - r * Wo;
     float z[CP];
-    full_res_logits<CP, T>(low, ld, H, W, n, r, s, sh, sw, z);
+    full_res_logits<CP, T>(low, ld, H, W, px.n, px.r, px.s, sh, sw, z);
     float m, se, zy;
     softmax_stats<CP>(z, C, y, m, se, zy, true);
     const float inv = 1.f / se;
-    float wy = 0.f;
-#pragma unroll
-    for (int c = 0; c < CP; ++c) wy = c == y ? w[c] : wy;
+    const float wy = pick<CP>(w, y);
 #pragma unroll
     for (int c = 0; c < CP; c += 4) {
       f32x4 o;
@@ -1135,20 +1133,13 @@ __global__ __launch_bounds__(256) void oh_up_grad_kernel(const T* __restrict__ l
         const int cc = c + j;
         o[j] = cc < C ? scale * (wy * __builtin_fmaf(z[cc], inv, cc == y ? -1.f : -0.f)) : 0.f;
       }
-      if constexpr (NCHW) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          if (c + j < C) dn[(c + j) * plane] = o[j];
-      } else {
-        st4(d + c, o);
-      }
+      store_quad<NCHW>(d, dn, c, C, plane, o);
     }
   }
 }
 
 inline bool oh_args_ok(long ld, int C, long total, float tau, long min_kept) {
-  return !(ld & 3) && C >= 1 && C <= CMAX && ld >= C && total >= 0 && total < (1L << 31) && std::isfinite(tau) &&
-         tau >= 0.f && min_kept >= 1;
+  return loss_geom_ok(ld, C) && total >= 0 && total < (1L << 31) && std::isfinite(tau) && tau >= 0.f && min_kept >= 1;
 }
 
 template <typename T, bool EVAL>
@@ -1158,24 +1149,15 @@ int oh_loss_impl(const T* low, long ld, int N, int H, int W, int C, const long l
   const long total = (long)N * Ho * Wo;
   if (!oh_args_ok(ld, C, total, tau, min_kept) || (EVAL && !confusion)) return (int)hipErrorInvalidValue;
   const int nb = loss_blocks(total);
-  const float sh = Ho > 1 ? (float)(H - 1) / (float)(Ho - 1) : 0.f;
-  const float sw = Wo > 1 ? (float)(W - 1) / (float)(Wo - 1) : 0.f;
+  const UpScale up = up_scale(H, W, Ho, Wo);
   float* lbuf = work;
   unsigned* ctl = reinterpret_cast<unsigned*>(work + total);
   float* part = work + total + OH_CTL;
   // every call clears its histograms and counters on the stream: a replayed tape never sees the last step's bins
   const hipError_t e = hipMemsetAsync(ctl, 0, sizeof(unsigned) * OH_CTL, stream);
   if (e != hipSuccess) return (int)e;
-#define SEG_OH_L(CP)                                                                                         \
-  case CP:                                                                                                   \
-    hipLaunchKernelGGL((oh_up_loss_kernel<CP, T, EVAL>), dim3(nb), dim3(256), 0, stream, low, ld, N, H, W,    \
-                       C, labels, Ho, Wo, sh, sw, ignore_index, tau, lbuf, ctl,                              \
-                       (unsigned long long*)confusion);                                                      \
-    break
-  switch ((C + 3) & ~3) {
-    SEG_OH_L(4); SEG_OH_L(8); SEG_OH_L(12); SEG_OH_L(16); SEG_OH_L(20); SEG_OH_L(24); SEG_OH_L(28); SEG_OH_L(32);
-  }
-#undef SEG_OH_L
+  SEG_LAUNCH_CP(C, oh_up_loss_kernel, (T, EVAL), nb, stream, low, ld, N, H, W, C, labels, Ho, Wo, up.sh, up.sw,
+                ignore_index, tau, lbuf, ctl, (unsigned long long*)confusion)
   hipLaunchKernelGGL(oh_refine_kernel<1>, dim3(nb), dim3(256), 0, stream, lbuf, total, min_kept, ctl);
   hipLaunchKernelGGL(oh_refine_kernel<2>, dim3(nb), dim3(256), 0, stream, lbuf, total, min_kept, ctl);
   hipLaunchKernelGGL(oh_reduce_kernel, dim3(nb), dim3(256), 0, stream, lbuf, labels, total, min_kept, tau, cw, ctl,
@@ -1189,20 +1171,11 @@ int oh_grad_impl(const T* low, long ld, int N, int H, int W, int C, const long l
                  const float* cw, float tau, const float* work, const float* grad_out, const float* stats, void* dhigh,
                  long ldh, hipStream_t stream) {
   const long total = (long)N * Ho * Wo;
-  if (!oh_args_ok(ld, C, total, tau, 1) || (!NCHW && ((ldh & 3) || ldh < C))) return (int)hipErrorInvalidValue;
-  const float sh = Ho > 1 ? (float)(H - 1) / (float)(Ho - 1) : 0.f;
-  const float sw = Wo > 1 ? (float)(W - 1) / (float)(Wo - 1) : 0.f;
-  const int grid = (int)std::min<long>(seg_cdiv(total, 256), 8192);
+  if (!oh_args_ok(ld, C, total, tau, 1) || (!NCHW && !rows_ok(ldh, C))) return (int)hipErrorInvalidValue;
+  const UpScale up = up_scale(H, W, Ho, Wo);
   const unsigned* ctl = reinterpret_cast<const unsigned*>(work + total);
-#define SEG_OH_G(CP)                                                                                         \
-  case CP:                                                                                                   \
-    hipLaunchKernelGGL((oh_up_grad_kernel<CP, T, NCHW>), dim3(grid), dim3(256), 0, stream, low, ld, N, H, W, C,     \
-                       labels, Ho, Wo, sh, sw, tau, cw, work, ctl, grad_out, stats, dhigh, ldh);             \
-    break
-  switch ((C + 3) & ~3) {
-    SEG_OH_G(4); SEG_OH_G(8); SEG_OH_G(12); SEG_OH_G(16); SEG_OH_G(20); SEG_OH_G(24); SEG_OH_G(28); SEG_OH_G(32);
-  }
-#undef SEG_OH_G
+  SEG_LAUNCH_CP(C, oh_up_grad_kernel, (T, NCHW), grad_blocks(total), stream, low, ld, N, H, W, C, labels, Ho, Wo,
+                up.sh, up.sw, tau, cw, work, ctl, grad_out, stats, dhigh, ldh)
   SEG_RET_LAST();
 }
 
@@ -1333,12 +1306,10 @@ __global__ __launch_bounds__(256) void kd_up_loss_kernel(const T* __restrict__ l
     if (oob) bad += 1.f;
     const bool valid = !ign && !oob;
     if (!valid && !o.all) continue;
-    const int n = (int)(p / ((long)Ho * Wo));
-    const int rem = (int)(p - (long)n * Ho * Wo);
-    const int r = rem / Wo, s = rem - r * Wo;
+    const Pix px = pixel_of(p, Ho, Wo);
     float z[CP], u[CP];
-    full_res_logits<CP, T>(low, ld, H, W, n, r, s, sh, sw, z);
-    full_res_logits<CP, float>(te.rows, te.ld, te.H, te.W, n, r, s, te.sh, te.sw, u);
+    full_res_logits<CP, T>(low, ld, H, W, px.n, px.r, px.s, sh, sw, z);
+    full_res_logits<CP, float>(te.rows, te.ld, te.H, te.W, px.n, px.r, px.s, te.sh, te.sw, u);
     {
       float dz[CP], ez[CP], du[CP], eu[CP];
       const float sz = kd_softmax<CP>(z, C, invT, dz, ez);
@@ -1352,9 +1323,7 @@ __global__ __launch_bounds__(256) void kd_up_loss_kernel(const T* __restrict__ l
     }
     if (valid) {
       val += 1.f;
-      float wy = 0.f;
-#pragma unroll
-      for (int c = 0; c < CP; ++c) wy = c == (int)y ? w[c] : wy;
+      const float wy = pick<CP>(w, (int)y);
       cnt += wy;
       if (has_ce) {
         float m, se, zy;
@@ -1383,21 +1352,9 @@ __global__ __launch_bounds__(256) void kd_up_loss_kernel(const T* __restrict__ l
 // (kd_ignored) or #valid; 0/0 = nan as aten (CE is 0 and left out when ce == 0).
 __global__ void kd_finalize_kernel(const float* __restrict__ part, int nblk, double total, float ce, float kd,
                                    float T, int all, float* out) {
-  double l = 0.0, c = 0.0, b = 0.0, v = 0.0, k = 0.0;
-  for (int i = threadIdx.x; i < nblk; i += 64) {
-    l += part[5 * i];
-    c += part[5 * i + 1];
-    b += part[5 * i + 2];
-    v += part[5 * i + 3];
-    k += part[5 * i + 4];
-  }
-  for (int o = 32; o > 0; o >>= 1) {
-    l += __shfl_xor(l, o, 64);
-    c += __shfl_xor(c, o, 64);
-    b += __shfl_xor(b, o, 64);
-    v += __shfl_xor(v, o, 64);
-    k += __shfl_xor(k, o, 64);
-  }
+  double t[5];
+  column_sums_f64<5>(part, nblk, 5, t);
+  const double l = t[0], c = t[1], b = t[2], v = t[3], k = t[4];
   if (threadIdx.x == 0) {
     const double P = all ? total : v;
     const double CE = ce > 0.f ? l / c : 0.0;
@@ -1413,8 +1370,7 @@ __global__ void kd_finalize_kernel(const float* __restrict__ part, int nblk, dou
   }
 }
 
-// NCHW (seg_kd_upsample_grad_bf16io_nchw): dhigh is fp32 [N][C][Ho][Wo] instead of T rows, as in the seg_ohem_* twin --
-// the low-resolution gradient then sums unrounded terms, where bf16 rows put 2^-9 on every one of them.
+// NCHW (seg_kd_upsample_grad_bf16io_nchw): fp32 planes instead of T rows, as in the seg_ohem_* twin (store_quad).
 template <int CP, typename T, bool NCHW>
 __global__ __launch_bounds__(256) void kd_up_grad_kernel(const T* __restrict__ low, long ld, int N, int H, int W,
                                                          int C, KdTeacher te, const long long* __restrict__ labels,
@@ -1425,31 +1381,24 @@ __global__ __launch_bounds__(256) void kd_up_grad_kernel(const T* __restrict__ l
   const long plane = (long)Ho * Wo, total = (long)N * plane;
   const bool poisoned = stats[2] > 0.f, has_ce = o.ce > 0.f;
   const float nan = __builtin_nanf("");
-  const float sce = poisoned ? nan : has_ce ? gout[0] * o.ce / stats[1] : 0.f;          // g ce / D
+  const float sce = poisoned ? nan : has_ce ? gout[0] * o.ce / stats[1] : 0.f;                  // g ce / D
   const float skd = poisoned ? nan : gout[0] * o.kd * o.T / (o.all ? (float)total : stats[3]);  // g kd T / |P|
   float w[CP];
   class_weights<CP>(o.cw, C, w);
   const float invT = 1.f / o.T;
   for (long p = blockIdx.x * (long)blockDim.x + threadIdx.x; p < total; p += (long)gridDim.x * blockDim.x) {
     const long long y = labels[p];
-    const int n = (int)(p / plane);
-    const int rem = (int)(p - (long)n * plane);
-    T* d = static_cast<T*>(dout) + p * ldh;                             // rows (!NCHW)
-    float* dn = static_cast<float*>(dout) + (long)n * C * plane + rem;  // class 0 of this pixel (NCHW)
+    const Pix px = pixel_of(p, Ho, Wo);
+    T* d = static_cast<T*>(dout) + p * ldh;
+    float* dn = static_cast<float*>(dout) + (long)px.n * C * plane + px.rem;
     const bool valid = !(y == ignore_index || y < 0 || y >= C);
-    if (!valid && !o.all) {  // out of range: the scales are NaN, the loss already is
-      if constexpr (NCHW) {
-        for (int c = 0; c < C; ++c) dn[c * plane] = 0.f;
-      } else {
-#pragma unroll
-        for (int c = 0; c < CP; c += 4) st4(d + c, f32x4{0.f, 0.f, 0.f, 0.f});
-      }
+    if (!valid && !o.all) {
+      zero_row<CP, NCHW>(d, dn, C, plane);
       continue;
     }
-    const int r = rem / Wo, s = rem - r * Wo;
     float z[CP], u[CP];
-    full_res_logits<CP, T>(low, ld, H, W, n, r, s, sh, sw, z);
-    full_res_logits<CP, float>(te.rows, te.ld, te.H, te.W, n, r, s, te.sh, te.sw, u);
+    full_res_logits<CP, T>(low, ld, H, W, px.n, px.r, px.s, sh, sw, z);
+    full_res_logits<CP, float>(te.rows, te.ld, te.H, te.W, px.n, px.r, px.s, te.sh, te.sw, u);
     float dz[CP], ez[CP], du[CP], eu[CP];
     const float sz = kd_softmax<CP>(z, C, invT, dz, ez);
     const float su = kd_softmax<CP>(u, C, invT, du, eu);
@@ -1460,9 +1409,7 @@ __global__ __launch_bounds__(256) void kd_up_grad_kernel(const T* __restrict__ l
       float m, se, zy;
       softmax_stats<CP>(z, C, (int)y, m, se, zy, true);  // z[c] = exp(z_c - max) now
       inv = 1.f / se;
-#pragma unroll
-      for (int c = 0; c < CP; ++c) kw = c == (int)y ? w[c] : kw;
-      kw *= sce;
+      kw = pick<CP>(w, (int)y) * sce;
     }
 #pragma unroll
     for (int c = 0; c < CP; c += 4) {
@@ -1473,25 +1420,18 @@ __global__ __launch_bounds__(256) void kd_up_grad_kernel(const T* __restrict__ l
         const float hard = with_ce ? kw * __builtin_fmaf(z[cc], inv, cc == (int)y ? -1.f : -0.f) : 0.f;
         ov[j] = cc < C ? __builtin_fmaf(skd, ez[cc] * iz - eu[cc] * iu, hard) : 0.f;
       }
-      if constexpr (NCHW) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          if (c + j < C) dn[(c + j) * plane] = ov[j];
-      } else {
-        st4(d + c, ov);
-      }
+      store_quad<NCHW>(d, dn, c, C, plane, ov);
     }
   }
 }
 
 inline bool kd_args_ok(long ld, int C, const float* teacher, long ldt, int Ht, int Wt, const KdOpt& o) {
-  return !(ld & 3) && !(ldt & 3) && C >= 1 && C <= CMAX && ld >= C && ldt >= C && Ht >= 1 && Wt >= 1 && teacher &&
-         kd_opt_ok(o);
+  return loss_geom_ok(ld, C) && rows_ok(ldt, C) && Ht >= 1 && Wt >= 1 && teacher && kd_opt_ok(o);
 }
 
 inline KdTeacher kd_teacher(const float* teacher, long ldt, int Ht, int Wt, int Ho, int Wo) {
-  return KdTeacher{teacher, ldt, Ht, Wt, Ho > 1 ? (float)(Ht - 1) / (float)(Ho - 1) : 0.f,
-                   Wo > 1 ? (float)(Wt - 1) / (float)(Wo - 1) : 0.f};
+  const UpScale up = up_scale(Ht, Wt, Ho, Wo);
+  return KdTeacher{teacher, ldt, Ht, Wt, up.sh, up.sw};
 }
 
 template <typename T>
@@ -1501,18 +1441,10 @@ int kd_loss_impl(const T* low, long ld, int N, int H, int W, int C, const float*
   if (!kd_args_ok(ld, C, teacher, ldt, Ht, Wt, o)) return (int)hipErrorInvalidValue;
   const long total = (long)N * Ho * Wo;
   const int nb = loss_blocks(total);
-  const float sh = Ho > 1 ? (float)(H - 1) / (float)(Ho - 1) : 0.f;
-  const float sw = Wo > 1 ? (float)(W - 1) / (float)(Wo - 1) : 0.f;
+  const UpScale up = up_scale(H, W, Ho, Wo);
   const KdTeacher te = kd_teacher(teacher, ldt, Ht, Wt, Ho, Wo);
-#define SEG_KD_L(CP)                                                                                         \
-  case CP:                                                                                                   \
-    hipLaunchKernelGGL((kd_up_loss_kernel<CP, T>), dim3(nb), dim3(256), 0, stream, low, ld, N, H, W, C, te,   \
-                       labels, Ho, Wo, sh, sw, ignore_index, work, o);                                       \
-    break
-  switch ((C + 3) & ~3) {
-    SEG_KD_L(4); SEG_KD_L(8); SEG_KD_L(12); SEG_KD_L(16); SEG_KD_L(20); SEG_KD_L(24); SEG_KD_L(28); SEG_KD_L(32);
-  }
-#undef SEG_KD_L
+  SEG_LAUNCH_CP(C, kd_up_loss_kernel, (T), nb, stream, low, ld, N, H, W, C, te, labels, Ho, Wo, up.sh, up.sw,
+                ignore_index, work, o)
   hipLaunchKernelGGL(kd_finalize_kernel, dim3(1), dim3(64), 0, stream, work, nb, (double)total, o.ce, o.kd, o.T,
                      o.all, out6);
   SEG_RET_LAST();
@@ -1522,22 +1454,11 @@ template <typename T, bool NCHW = false>
 int kd_grad_impl(const T* low, long ld, int N, int H, int W, int C, const float* teacher, long ldt, int Ht, int Wt,
                  const long long* labels, int Ho, int Wo, int ignore_index, KdOpt o, const float* grad_out,
                  const float* stats, void* dhigh, long ldh, hipStream_t stream) {
-  if (!kd_args_ok(ld, C, teacher, ldt, Ht, Wt, o) || (!NCHW && ((ldh & 3) || ldh < C)))
-    return (int)hipErrorInvalidValue;
-  const long total = (long)N * Ho * Wo;
-  const float sh = Ho > 1 ? (float)(H - 1) / (float)(Ho - 1) : 0.f;
-  const float sw = Wo > 1 ? (float)(W - 1) / (float)(Wo - 1) : 0.f;
+  if (!kd_args_ok(ld, C, teacher, ldt, Ht, Wt, o) || (!NCHW && !rows_ok(ldh, C))) return (int)hipErrorInvalidValue;
+  const UpScale up = up_scale(H, W, Ho, Wo);
   const KdTeacher te = kd_teacher(teacher, ldt, Ht, Wt, Ho, Wo);
-  const int grid = (int)std::min<long>(seg_cdiv(total, 256), 8192);
-#define SEG_KD_G(CP)                                                                                          \
-  case CP:                                                                                                    \
-    hipLaunchKernelGGL((kd_up_grad_kernel<CP, T, NCHW>), dim3(grid), dim3(256), 0, stream, low, ld, N, H, W, C, te, \
-                       labels, Ho, Wo, sh, sw, ignore_index, grad_out, stats, dhigh, ldh, o);                 \
-    break
-  switch ((C + 3) & ~3) {
-    SEG_KD_G(4); SEG_KD_G(8); SEG_KD_G(12); SEG_KD_G(16); SEG_KD_G(20); SEG_KD_G(24); SEG_KD_G(28); SEG_KD_G(32);
-  }
-#undef SEG_KD_G
+  SEG_LAUNCH_CP(C, kd_up_grad_kernel, (T, NCHW), grad_blocks((long)N * Ho * Wo), stream, low, ld, N, H, W, C, te,
+                labels, Ho, Wo, up.sh, up.sw, ignore_index, grad_out, stats, dhigh, ldh, o)
   SEG_RET_LAST();
 }
 
@@ -1606,7 +1527,7 @@ SEG_API int seg_kd_upsample_grad_bf16io(const __bf16* low, long ld, int N, int H
                       KdOpt{class_weight, ce, kd, temperature, kd_ignored != 0}, grad_out, stats, dhigh, ldh, stream);
 }
 // seg_kd_upsample_grad_bf16io with the full-resolution gradient written as fp32 NCHW [N][C][Ho][Wo]: follow with
-// seg_upsample_bwd_bf16io(nchw_grad = 1, ac = 1).
+// seg_upsample_bwd_bf16io(nchw_grad = 1, ac = 2).
 SEG_API int seg_kd_upsample_grad_bf16io_nchw(const __bf16* low, long ld, int N, int H, int W, int C,
                                              const float* teacher, long ldt, int Ht, int Wt, const long long* labels,
                                              int Ho, int Wo, int ignore_index, const float* class_weight, float ce,

@@ -47,6 +47,7 @@ import contextlib
 import ctypes
 import math
 import os
+from types import SimpleNamespace
 from typing import NamedTuple
 
 import torch
@@ -1199,13 +1200,14 @@ class Run:
         self.defer = prog.wgrad_defer()  # (from, at) of the deferred parameter gradients, or None
         # the fused loss's forward (_loss_forward), read by its backward
         self.target = self.weight = self.stats = None  # labels, class weights, the [loss, count, ...] buffer
-        self.label_smoothing = 0.0
-        self.plain_loss = True  # no class weights, smoothing or "sum": the seg_ce_* kernels (else seg_cew_*)
-        self.sl = None          # (ce, dice, focal_gamma, dice_smooth) of a SegLoss: the seg_sl_* kernels
-        self.ohem = None        # (tau, workspace) of an OhemCELoss: the seg_ohem_* kernels
-        self.sl_table = None    # their per-class Dice gradient coefficients, written by the loss's finalize
-        self.kd = None          # the Distill of a DistillLoss: the seg_kd_* kernels
-        self.teacher = None     # ... and the teacher's low-resolution logits (fp32 NHWC rows)
+        self.loss = None        # its kernel family, options and buffers (a Loss)
+        self.teacher = None     # a DistillLoss: the teacher's low-resolution logits (fp32 NHWC rows)
+
+    @property
+    def ohem(self):
+        """(tau, workspace) of an OhemCELoss's forward, else None."""
+        L = self.loss
+        return (L.opt[0], L.work) if L is not None and L.fam is LOSS_FAMILIES["ohem"] else None
 
     def k(self, name: str) -> str:
         """C-ABI entry point of an activation kernel for this run's storage type."""
@@ -1731,6 +1733,68 @@ def _plain_loss(weight, label_smoothing, reduction):
     return weight is None and label_smoothing == 0.0 and reduction == "mean"
 
 
+class LossFamily(NamedTuple):
+    """One kernel family of the fused loss (csrc/loss.hip): seg_<stem>_upsample_loss / _eval / _grad and what differs
+    between the families' calls.  fwd / grad return a call's arguments up to (work, stats) / (grad_out, stats) and
+    whatever the ABI puts right behind them, from the argument groups of _loss_args and the family's options;
+    _loss_forward appends (confusion,) stream, _loss_backward the gradient buffer, (its leading dimension,) stream."""
+    stem: str
+    nstats: int   # floats of the stats buffer; [loss, D or #valid, #out-of-range labels] lead in every family
+    has_eval: bool
+    nchw: object  # None, or the suffix behind _bf16io of the twin whose gradient is fp32 NCHW instead of bf16 rows
+    ac: int       # of the seg_upsample_bwd behind the gradient: 2 = the transpose of the kd kernels' own blend (lin_ac)
+    fwd: object
+    grad: object
+
+
+def _kd_head(a, o):  # the teacher's rows sit before the labels
+    return a.head + (a.teacher.data_ptr(), a.teacher.shape[3], o.Ht, o.Wt) + a.labels
+
+
+def _kd_opts(a, o):
+    return (a.w, o.ce, o.kd, o.temperature, int(o.kd_ignored))
+
+
+# opt: cew (eps, reduction), sl (eps, ce, dice, focal_gamma, dice_smooth), ohem (tau, min_kept), kd a Distill
+LOSS_FAMILIES = {f.stem: f for f in (
+    LossFamily("ce", 3, True, None, 1,
+               lambda a, o: a.head + a.labels + a.out,
+               lambda a, o: a.head + a.labels + a.out),
+    LossFamily("cew", 4, True, None, 1,
+               lambda a, o: a.head + a.labels + (a.w, o[0], REDUCTIONS[o[1]]) + a.out,
+               lambda a, o: a.head + a.labels + (a.w, o[0]) + a.out),
+    LossFamily("sl", 6, True, None, 1,  # the table of Dice coefficients behind the stats
+               lambda a, o: a.head + a.labels + (a.w,) + tuple(o) + a.out + (a.table.data_ptr(),),
+               lambda a, o: a.head + a.labels + (a.w,) + tuple(o[:4]) + a.out + (a.table.data_ptr(),)),
+    LossFamily("ohem", 6, True, "", 1,  # the gradient reads the per-pixel losses back from the workspace
+               lambda a, o: a.head + a.labels + (a.w,) + tuple(o) + a.out,
+               lambda a, o: a.head + a.labels + (a.w, o[0], a.work.data_ptr()) + a.out),
+    LossFamily("kd", 6, False, "_nchw", 2,
+               lambda a, o: _kd_head(a, o) + _kd_opts(a, o) + a.out,
+               lambda a, o: _kd_head(a, o) + _kd_opts(a, o) + a.out),
+)}
+
+
+class Loss(NamedTuple):
+    """A fused loss's forward as its backward needs it (Run.loss)."""
+    fam: LossFamily
+    opt: tuple             # the family's options (LOSS_FAMILIES)
+    work: torch.Tensor     # the forward's workspace
+    table: object = None   # sl: the per-class Dice gradient coefficients, written by the loss's finalize
+
+
+def _loss_args(run, ignore_index, out):
+    """The argument groups of a fused-loss call at the run's current labels, class weights and teacher; out: the
+    (work, stats) of a forward or the (grad_out, stats) of a gradient call."""
+    prog, lo, L = run.prog, run.prog.logits, run.loss
+    Ho, Wo = prog.out_hw
+    return SimpleNamespace(head=(run.ptr(lo), lo.ld, prog.N, lo.H, lo.W, lo.C),
+                           labels=(run.target.data_ptr(), Ho, Wo, ignore_index),
+                           w=run.weight.data_ptr() if run.weight is not None else 0,
+                           teacher=run.teacher, work=L.work, table=L.table,
+                           out=(out.data_ptr(), run.stats.data_ptr()))
+
+
 def _loss_forward(run, t, ignore_index, confusion=None, weight=None, label_smoothing=0.0, reduction="mean", sl=None):
     """Fused final upsample + CrossEntropy over the run's low-res logits: stats = [loss, count, #bad labels].
     confusion (int64 [C, C], "metrics" mode): the same pass also adds every valid pixel to
@@ -1742,79 +1806,36 @@ def _loss_forward(run, t, ignore_index, confusion=None, weight=None, label_smoot
     #valid, #kept, cut]; their workspace starts with the per-pixel losses (4 B per pixel), which the gradient
     kernel reads back.
     sl = Distill(ce, kd, temperature, kd_ignored, Ht, Wt) of a seg_amd.DistillLoss: the seg_kd_* kernels over
-    run.teacher (fp32 NHWC rows [N, Ht, Wt, round4(C)]), stats = [loss, D, #bad labels, #valid, CE, KD]."""
-    prog, lo, s = run.prog, run.prog.logits, run.stream
-    N = prog.N
+    run.teacher (fp32 NHWC rows [N, Ht, Wt, round4(C)], a tape external like the class weights), stats = [loss, D,
+    #bad labels, #valid, CE, KD]."""
+    prog, s = run.prog, run.stream
     Ho, Wo = prog.out_hw
-    run.target, run.weight, run.label_smoothing = t, weight, label_smoothing
-    run.plain_loss = sl is None and _plain_loss(weight, label_smoothing, reduction)
-    run.sl = run.ohem = run.kd = None
+    pixels = prog.N * Ho * Wo
+    run.target, run.weight = t, weight
     if isinstance(sl, Distill):
-        # stats = [loss, D, #bad labels, #valid, CE, KD]; the teacher's rows (run.teacher, set by the plan) are a
-        # tape external like the class weights
-        if confusion is not None:
-            raise ValueError("validation does not distil: evaluate the criterion's hard() term")
-        te = run.teacher
-        stats = run.tmp(6)
-        work = run.tmp(query("seg_kd_workspace_floats", N * Ho * Wo))
-        run.call(run.k("seg_kd_upsample_loss"), run.ptr(lo), lo.ld, N, lo.H, lo.W, lo.C, te.data_ptr(), te.shape[3],
-                 sl.Ht, sl.Wt, t.data_ptr(), Ho, Wo, ignore_index, weight.data_ptr() if weight is not None else 0,
-                 sl.ce, sl.kd, sl.temperature, int(sl.kd_ignored), work.data_ptr(), stats.data_ptr(), s)
-        run.kd = sl
-        run.stats = stats
-        return stats
-    if isinstance(sl, Ohem):
+        fam, opt = LOSS_FAMILIES["kd"], sl
+    elif isinstance(sl, Ohem):
         from .losses import resolve_min_kept
-        tau = -math.log(sl.thresh)  # float64 here, a float in the kernels
-        stats = run.tmp(6)
-        work = run.tmp(query("seg_ohem_workspace_floats", N * Ho * Wo))
-        args = (run.ptr(lo), lo.ld, N, lo.H, lo.W, lo.C, t.data_ptr(), Ho, Wo, ignore_index,
-                weight.data_ptr() if weight is not None else 0, tau, resolve_min_kept(sl.min_kept, N * Ho * Wo),
-                work.data_ptr(), stats.data_ptr())
-        if confusion is None:
-            run.call(run.k("seg_ohem_upsample_loss"), *args, s)
-        else:
-            run.call(run.k("seg_ohem_upsample_eval"), *args, confusion.data_ptr(), s)
-        run.ohem = (tau, work)
-        run.stats = stats
-        return stats
-    run.sl = sl
-    if sl is not None:
-        ce, dice, gamma, smooth = sl
-        stats = run.tmp(6)
-        run.sl_table = run.tmp(64)
-        work = run.tmp(query("seg_sl_workspace_floats", N * Ho * Wo))
-        args = (run.ptr(lo), lo.ld, N, lo.H, lo.W, lo.C, t.data_ptr(), Ho, Wo, ignore_index,
-                weight.data_ptr() if weight is not None else 0, label_smoothing, ce, dice, gamma, smooth,
-                work.data_ptr(), stats.data_ptr(), run.sl_table.data_ptr())
-        if confusion is None:
-            run.call(run.k("seg_sl_upsample_loss"), *args, s)
-        else:
-            run.call(run.k("seg_sl_upsample_eval"), *args, confusion.data_ptr(), s)
-        run.stats = stats
-        return stats
-    if not run.plain_loss:
-        stats = run.tmp(4)  # loss, D, #out-of-range labels, #valid
-        work = run.tmp(query("seg_cew_workspace_floats", N * Ho * Wo))
-        args = (run.ptr(lo), lo.ld, N, lo.H, lo.W, lo.C, t.data_ptr(), Ho, Wo, ignore_index,
-                weight.data_ptr() if weight is not None else 0, label_smoothing, REDUCTIONS[reduction],
-                work.data_ptr(), stats.data_ptr())
-        if confusion is None:
-            run.call(run.k("seg_cew_upsample_loss"), *args, s)
-        else:
-            run.call(run.k("seg_cew_upsample_eval"), *args, confusion.data_ptr(), s)
-        run.stats = stats
-        return stats
-    stats = run.tmp(3)  # loss, #valid, #out-of-range labels
-    work = run.tmp(query("seg_ce_workspace_floats", N * Ho * Wo))
-    if confusion is None:
-        run.call(run.k("seg_ce_upsample_loss"), run.ptr(lo), lo.ld, N, lo.H, lo.W, lo.C, t.data_ptr(), Ho, Wo,
-                 ignore_index, work.data_ptr(), stats.data_ptr(), s)
+        # tau: float64 here, a float in the kernels
+        fam, opt = LOSS_FAMILIES["ohem"], (-math.log(sl.thresh), resolve_min_kept(sl.min_kept, pixels))
+    elif sl is not None:
+        fam, opt = LOSS_FAMILIES["sl"], (label_smoothing,) + tuple(sl)
+    elif not _plain_loss(weight, label_smoothing, reduction):
+        fam, opt = LOSS_FAMILIES["cew"], (label_smoothing, reduction)
     else:
-        run.call(run.k("seg_ce_upsample_eval"), run.ptr(lo), lo.ld, N, lo.H, lo.W, lo.C, t.data_ptr(), Ho, Wo,
-                 ignore_index, work.data_ptr(), stats.data_ptr(), confusion.data_ptr(), s)
-    run.stats = stats
-    return stats
+        fam, opt = LOSS_FAMILIES["ce"], ()
+    if confusion is not None and not fam.has_eval:
+        raise ValueError("validation does not distil: evaluate the criterion's hard() term")
+    run.stats = run.tmp(fam.nstats)
+    table = run.tmp(64) if fam.stem == "sl" else None
+    work = run.tmp(query(f"seg_{fam.stem}_workspace_floats", pixels))
+    run.loss = Loss(fam, opt, work, table)
+    args = fam.fwd(_loss_args(run, ignore_index, work), opt)
+    if confusion is None:
+        run.call(run.k(f"seg_{fam.stem}_upsample_loss"), *args, s)
+    else:
+        run.call(run.k(f"seg_{fam.stem}_upsample_eval"), *args, confusion.data_ptr(), s)
+    return run.stats
 
 
 def _loss_backward(run, g, ignore_index):
@@ -1822,67 +1843,20 @@ def _loss_backward(run, g, ignore_index):
     prog, lo, s = run.prog, run.prog.logits, run.stream
     N = prog.N
     Ho, Wo = prog.out_hw
-    if run.ohem is not None and run.io:
-        # the bf16io twin: the full-resolution gradient in fp32 NCHW, as behind the model's logits (bf16 rows would
-        # round every term of the low-resolution gradient's sums)
-        w = run.weight
-        tau, work = run.ohem
+    fam, opt = run.loss.fam, run.loss.opt
+    # the bf16io twins of ohem and kd: the full-resolution gradient in fp32 NCHW, as behind the model's logits (bf16
+    # rows would round every term of the low-resolution gradient's sums)
+    nchw = run.io and fam.nchw is not None
+    if nchw:
         dhigh = torch.empty(max(N * lo.C * Ho * Wo, 1), device=run.device, dtype=torch.float32)
-        run.keep.append(dhigh)
-        run.call("seg_ohem_upsample_grad_bf16io", run.ptr(lo), lo.ld, N, lo.H, lo.W, lo.C, run.target.data_ptr(), Ho,
-                 Wo, ignore_index, w.data_ptr() if w is not None else 0, tau, work.data_ptr(), g.data_ptr(),
-                 run.stats.data_ptr(), dhigh.data_ptr(), s)
-        run.call(run.k("seg_upsample_bwd"), dhigh.data_ptr(), 0, 1, N, Ho, Wo, lo.C, run.gptr(lo), lo.ld, lo.H, lo.W,
-                 1, 0, s)
-        run.mark_written(lo)
-        run.backward_from_logits()
-        return
-    if run.kd is not None and run.io:
-        # as for an OhemCELoss: the full-resolution gradient in fp32 NCHW
-        w, te, kd = run.weight, run.teacher, run.kd
-        dhigh = torch.empty(max(N * lo.C * Ho * Wo, 1), device=run.device, dtype=torch.float32)
-        run.keep.append(dhigh)
-        run.call("seg_kd_upsample_grad_bf16io_nchw", run.ptr(lo), lo.ld, N, lo.H, lo.W, lo.C, te.data_ptr(),
-                 te.shape[3], kd.Ht, kd.Wt, run.target.data_ptr(), Ho, Wo, ignore_index,
-                 w.data_ptr() if w is not None else 0, kd.ce, kd.kd, kd.temperature, int(kd.kd_ignored),
-                 g.data_ptr(), run.stats.data_ptr(), dhigh.data_ptr(), s)
-        # ac = 2: the transpose of the kd kernels' own blend (lin_ac)
-        run.call(run.k("seg_upsample_bwd"), dhigh.data_ptr(), 0, 1, N, Ho, Wo, lo.C, run.gptr(lo), lo.ld, lo.H, lo.W,
-                 2, 0, s)
-        run.mark_written(lo)
-        run.backward_from_logits()
-        return
-    dhigh = torch.empty(max(N * Ho * Wo * lo.ld, 1), device=run.device, dtype=run.store)
+    else:
+        dhigh = torch.empty(max(N * Ho * Wo * lo.ld, 1), device=run.device, dtype=run.store)
     run.keep.append(dhigh)
-    if run.kd is not None:  # the forward's options (_loss_forward)
-        w, te, kd = run.weight, run.teacher, run.kd
-        run.call("seg_kd_upsample_grad", run.ptr(lo), lo.ld, N, lo.H, lo.W, lo.C, te.data_ptr(), te.shape[3],
-                 kd.Ht, kd.Wt, run.target.data_ptr(), Ho, Wo, ignore_index, w.data_ptr() if w is not None else 0,
-                 kd.ce, kd.kd, kd.temperature, int(kd.kd_ignored), g.data_ptr(), run.stats.data_ptr(),
-                 dhigh.data_ptr(), lo.ld, s)
-    elif run.ohem is not None:  # the forward's options (_loss_forward)
-        w = run.weight
-        tau, work = run.ohem
-        run.call("seg_ohem_upsample_grad", run.ptr(lo), lo.ld, N, lo.H, lo.W, lo.C, run.target.data_ptr(), Ho,
-                 Wo, ignore_index, w.data_ptr() if w is not None else 0, tau, work.data_ptr(), g.data_ptr(),
-                 run.stats.data_ptr(), dhigh.data_ptr(), lo.ld, s)
-    elif run.sl is not None:  # the forward's options (_loss_forward)
-        w = run.weight
-        ce, dice, gamma, _ = run.sl
-        run.call(run.k("seg_sl_upsample_grad"), run.ptr(lo), lo.ld, N, lo.H, lo.W, lo.C, run.target.data_ptr(), Ho,
-                 Wo, ignore_index, w.data_ptr() if w is not None else 0, run.label_smoothing, ce, dice, gamma,
-                 g.data_ptr(), run.stats.data_ptr(), run.sl_table.data_ptr(), dhigh.data_ptr(), lo.ld, s)
-    elif run.plain_loss:
-        run.call(run.k("seg_ce_upsample_grad"), run.ptr(lo), lo.ld, N, lo.H, lo.W, lo.C, run.target.data_ptr(), Ho,
-                 Wo, ignore_index, g.data_ptr(), run.stats.data_ptr(), dhigh.data_ptr(), lo.ld, s)
-    else:  # the forward's options (_loss_forward)
-        w = run.weight
-        run.call(run.k("seg_cew_upsample_grad"), run.ptr(lo), lo.ld, N, lo.H, lo.W, lo.C, run.target.data_ptr(), Ho,
-                 Wo, ignore_index, w.data_ptr() if w is not None else 0, run.label_smoothing, g.data_ptr(),
-                 run.stats.data_ptr(), dhigh.data_ptr(), lo.ld, s)
-    # a DistillLoss: ac = 2, the transpose of the kd kernels' own blend (lin_ac); the other families as they were
-    run.call(run.k("seg_upsample_bwd"), dhigh.data_ptr(), lo.ld, 0, N, Ho, Wo, lo.C, run.gptr(lo), lo.ld, lo.H, lo.W,
-             2 if run.kd is not None else 1, 0, s)
+    ldh = () if nchw else (lo.ld,)
+    run.call(run.k(f"seg_{fam.stem}_upsample_grad") + (fam.nchw if nchw else ""),
+             *fam.grad(_loss_args(run, ignore_index, g), opt), dhigh.data_ptr(), *ldh, s)
+    run.call(run.k("seg_upsample_bwd"), dhigh.data_ptr(), 0 if nchw else lo.ld, int(nchw), N, Ho, Wo, lo.C,
+             run.gptr(lo), lo.ld, lo.H, lo.W, fam.ac, 0, s)
     run.mark_written(lo)
     run.backward_from_logits()
 

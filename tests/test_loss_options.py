@@ -166,3 +166,39 @@ def test_argument_validation_without_gpu(lib):
         assert grad(g, ld=10) == 1 and grad(g, ldh=10) == 1 and grad(g, Cn=33, ld=36, ldh=36) == 1
     assert _lib.query("seg_cew_workspace_floats", 4 * 256 * 512) >= 5
     assert _lib.query("seg_cew_workspace_floats", 1) == 5
+
+
+def test_every_family_checks_its_geometry_before_any_launch(lib):
+    # one table of bad geometries for seg_ce_*, seg_cew_*, seg_sl_* and seg_kd_* (seg_ohem_*: tests/test_ohem_loss.py):
+    # every entry point returns hipErrorInvalidValue (1) with every buffer NULL, so nothing was launched.  The options
+    # are valid ones and the teacher / confusion pointers non-NULL (never read): the geometry is what is refused.
+    head = lambda a: (None, a["ld"], 1, 4, 4, a["C"])
+    lab = (None, 8, 8, -100)
+    te = (16, 12, 4, 4)  # teacher rows, ldt, Ht, Wt
+    fams = {
+        "seg_ce": dict(fwd=lambda a: head(a) + lab + (None, None), grad=lambda a: head(a) + lab),
+        "seg_cew": dict(fwd=lambda a: head(a) + lab + (None, 0.1, 0, None, None),
+                        grad=lambda a: head(a) + lab + (None, 0.1)),
+        "seg_sl": dict(fwd=lambda a: head(a) + lab + (None, 0.0, 1.0, 0.5, 0.0, 1.0, None, None, None),
+                       grad=lambda a: head(a) + lab + (None, 0.0, 1.0, 0.5, 0.0), table=(None,)),
+        "seg_kd": dict(fwd=lambda a: head(a) + te + lab + (None, 1.0, 0.5, 2.0, 1, None, None),
+                       grad=lambda a: head(a) + te + lab + (None, 1.0, 0.5, 2.0, 1), eval=False),
+    }
+    ok = dict(ld=12, C=10, ldh=12, conf=8)
+    table = (dict(C=0), dict(C=33, ld=36, ldh=36), dict(ld=10), dict(ld=8), dict(ldh=10), dict(ldh=8), dict(conf=None))
+    for stem, fam in fams.items():
+        for bad in table:
+            a = dict(ok, **bad)
+            for sfx in ("", "_bf16io"):
+                if "ldh" not in bad or "C" in bad:
+                    if "conf" not in bad:
+                        assert getattr(lib, f"{stem}_upsample_loss{sfx}")(*fam["fwd"](a), None) == 1, (stem, sfx, bad)
+                    if fam.get("eval", True):
+                        assert getattr(lib, f"{stem}_upsample_eval{sfx}")(*fam["fwd"](a), a["conf"], None) == 1, \
+                            (stem, sfx, bad)
+                if "conf" not in bad:
+                    args = fam["grad"](a) + (None, None) + fam.get("table", ()) + (None,)
+                    assert getattr(lib, f"{stem}_upsample_grad{sfx}")(*args, a["ldh"], None) == 1, (stem, sfx, bad)
+            if stem == "seg_kd" and "ldh" not in bad and "conf" not in bad:  # the fp32 NCHW twin has no ldh
+                args = fam["grad"](a) + (None, None, None)
+                assert lib.seg_kd_upsample_grad_bf16io_nchw(*args, None) == 1, bad
