@@ -606,6 +606,47 @@ int seg_kd_upsample_grad(const float* low, long ld, int N, int H, int W, int C,
  * channels C..ldo-1 written as 0), one launch: a model's low-resolution logits as seg_kd_*'s `teacher`
  * (model.forward_low_logits).  The _bf16io twin widens seg_bf16 rows. */
 int seg_low_logits_f32(const float* low, long ld, long rows, int C, float* out, long ldo, hipStream_t stream);
+/* seg_amd.BinarySegLoss: a one-logit model's sigmoid loss -- binary cross-entropy with pos_weight and a focal
+ * exponent, plus soft Dice of the foreground -- fused with the same upsample (the full-resolution logits never
+ * stored, no float atomics: two calls on the same inputs agree bitwise).  C must be 1: rows of ld floats (ld % 4 ==
+ * 0) whose lane 0 is the logit; the pad lanes are loaded and never used.  Labels t_p are 0, 1 or ignore_index;
+ * anything else is out of range.  Over the valid pixels V, with z_p the pixel's upsampled logit (bitwise lane 0 of
+ * what the other families recompute), s_p = sigmoid(z_p), pt_p = s_p where t_p = 1 else 1 - s_p, w_p = pos_weight
+ * where t_p = 1 else 1:
+ *   F    = sum_V w_p (1 - pt_p)^gamma (-log pt_p) / |V|       (the divisor is |V|, not sum w: with gamma = 0 it is
+ *          nn.BCEWithLogitsLoss(pos_weight)'s mean)
+ *   I = sum_V s_p t_p,  S = sum_V s_p,  T = sum_V t_p,  U = S + T + dice_smooth,  Dice = 1 - (2 I + dice_smooth) / U
+ *   loss = bce F + dice Dice   (a term whose coefficient is 0 is left out)
+ *   dloss/dz_p = g bce / |V| (t_p ? -1 : 1) w_p (1 - pt)^gamma ((1 - pt) + gamma pt (-log pt))
+ *                - g dice (a t_p - b) s_p (1 - s_p),    a = 2 / U,  b = (2 I + dice_smooth) / U^2.
+ * -log sigmoid(x) is max(-x, 0) + log1p(exp(-|x|)) and sigmoid comes from exp(-|x|): every value is finite for any
+ * finite logit, and (1 - pt)^gamma is exactly 0 where 1 - pt rounds to 0.
+ * stats8 = [loss, #valid pixels, #labels outside {0, 1} that are not ignore_index, #valid pixels, F, Dice, a, b]: the
+ * first four slots are seg_cew_*'s out4 (D = #valid); a and b are written by _loss / _eval and read by _grad, whose
+ * `stats8` is theirs.  No valid pixel gives a NaN F (0/0, as aten); an out-of-range label is counted, put in no bin,
+ * and makes the loss and every gradient NaN.  `work` >= seg_bce_workspace_floats(N*Ho*Wo).
+ * _eval: the same loss and stats, bitwise, and confusion[t_p * 2 + (z_p > zthr)] += 1 for every valid pixel (int64
+ * [2][2] in device memory, added to; 64-bit integer atomics).  zthr = log(threshold / (1 - threshold)); the comparison
+ * is strict, so a tie or a NaN logit is background -- "first maximum wins" for the two-class view [0, z].
+ * _grad: dhigh is fp32 [N][Ho][Wo], ONE float per pixel and no `ldh`, in the _bf16io twins too (their `low` is
+ * seg_bf16): at C = 1 this is the NCHW plane seg_upsample_bwd(nchw_grad = 1, ac = 2) reads, it costs 4 B a pixel where
+ * a round4(C) row costs 16, and the low-resolution gradient sums unrounded terms (the reason given at
+ * seg_ohem_upsample_grad_bf16io).  Exactly 0 on ignored pixels.
+ * hipErrorInvalidValue before any launch: C != 1, ld % 4 != 0, pos_weight <= 0, a negative bce, dice or focal_gamma,
+ * bce and dice both 0, dice_smooth <= 0, any of them non-finite, or (_eval) confusion NULL. */
+long seg_bce_workspace_floats(long pixels);
+int seg_bce_upsample_loss(const float* low, long ld, int N, int H, int W, int C,
+                          const long long* labels, int Ho, int Wo, int ignore_index,
+                          float pos_weight, float bce, float dice, float focal_gamma, float dice_smooth,
+                          float* work, float* stats8, hipStream_t stream);
+int seg_bce_upsample_eval(const float* low, long ld, int N, int H, int W, int C,
+                          const long long* labels, int Ho, int Wo, int ignore_index,
+                          float pos_weight, float bce, float dice, float focal_gamma, float dice_smooth,
+                          float* work, float* stats8, float zthr, long long* confusion, hipStream_t stream);
+int seg_bce_upsample_grad(const float* low, long ld, int N, int H, int W, int C,
+                          const long long* labels, int Ho, int Wo, int ignore_index,
+                          float pos_weight, float bce, float dice, float focal_gamma,
+                          const float* grad_out, const float* stats8, float* dhigh, hipStream_t stream);
 
 /* ---- inference (inference.py: preprocess_image :28-46, model.eval() forward
  *      :23-25,162-163, overlay_predictions' argmax + resize :64-70) ---------- */
@@ -632,6 +673,11 @@ int seg_preprocess_bgr(const unsigned char* frame, int N, int Hf, int Wf, long r
  * resized to the frame with cv2 INTER_NEAREST.  First maximum wins. */
 int seg_argmax_nearest(const float* low, long ld, int N, int H, int W, int C, int Hm, int Wm,
                        unsigned char* mask, int Hf, int Wf, hipStream_t stream);
+/* seg_argmax_nearest for a one-logit model (rows of ld floats, ld % 4 == 0, lane 0 the logit): mask = 1 where the
+ * upsampled logit of the nearest model pixel is > zthr = log(threshold / (1 - threshold)), else 0.  Strict: a tie or
+ * a NaN logit gives 0.  hipErrorInvalidValue for ld % 4 != 0, a non-positive size or a NaN zthr. */
+int seg_threshold_nearest(const float* low, long ld, int N, int H, int W, int Hm, int Wm, float zthr,
+                          unsigned char* mask, int Hf, int Wf, hipStream_t stream);
 /* seg_argmax_nearest for video: the class of the exponential moving average over the frames of the
  * per-pixel class probabilities.  Per model pixel (Hm x Wm), in fp32: z = its upsampled logits (as
  * seg_upsample_to_nchw forms them), p = softmax(z); s = p when *fresh != 0 (or alpha == 1), else
@@ -818,6 +864,15 @@ int seg_kd_upsample_grad_bf16io_nchw(const seg_bf16* low, long ld, int N, int H,
     dhigh_nchw, hipStream_t stream);
 int seg_low_logits_f32_bf16io(const seg_bf16* low, long ld, long rows, int C, float* out, long ldo, hipStream_t
     stream);
+int seg_bce_upsample_loss_bf16io(const seg_bf16* low, long ld, int N, int H, int W, int C, const long long* labels, int
+    Ho, int Wo, int ignore_index, float pos_weight, float bce, float dice, float focal_gamma, float dice_smooth, float*
+    work, float* stats8, hipStream_t stream);
+int seg_bce_upsample_eval_bf16io(const seg_bf16* low, long ld, int N, int H, int W, int C, const long long* labels, int
+    Ho, int Wo, int ignore_index, float pos_weight, float bce, float dice, float focal_gamma, float dice_smooth, float*
+    work, float* stats8, float zthr, long long* confusion, hipStream_t stream);
+int seg_bce_upsample_grad_bf16io(const seg_bf16* low, long ld, int N, int H, int W, int C, const long long* labels, int
+    Ho, int Wo, int ignore_index, float pos_weight, float bce, float dice, float focal_gamma, const float* grad_out,
+    const float* stats8, float* dhigh, hipStream_t stream);
 int seg_upsample_fwd_bf16io(const seg_bf16* in, long ldin, int N, int H, int W, int C, seg_bf16* out, long ldout, int
     Ho, int Wo, int ac, hipStream_t stream);
 int seg_upsample_bwd_bf16io(const void* dout, long ldout, int nchw_grad, int N, int Ho, int Wo, int C, seg_bf16* din,

@@ -241,6 +241,34 @@ __global__ __launch_bounds__(256) void argmax_nearest_kernel(const float* __rest
   }
 }
 
+// One-logit models (seg_threshold_nearest): the foreground bit of model pixel (ym, xm), z > zthr for the pixel's one
+// upsampled logit -- model_class's taps and blend, lane 0 (the row's pad lanes are loaded with it and never used).
+// Strict: a tie or a NaN is background, "first maximum wins" for the two-class view [0, z].
+__device__ __forceinline__ int model_foreground(const float* __restrict__ base, long ld, int H, int W, int ym, int xm,
+                                                float sh, float sw, float zthr) {
+  const Lin lh = lin_index(ym, H, sh, 1), lw = lin_index(xm, W, sw, 1);
+  const f32x4 v00 = ld4(base + ((long)lh.i0 * W + lw.i0) * ld);
+  const f32x4 v01 = ld4(base + ((long)lh.i0 * W + lw.i1) * ld);
+  const f32x4 v10 = ld4(base + ((long)lh.i1 * W + lw.i0) * ld);
+  const f32x4 v11 = ld4(base + ((long)lh.i1 * W + lw.i1) * ld);
+  return bilerp4(v00, v01, v10, v11, lh, lw)[0] > zthr ? 1 : 0;
+}
+
+// argmax_nearest_kernel for one logit: mask[n][yf][xf] = foreground bit of the nearest model pixel.
+__global__ __launch_bounds__(256) void threshold_nearest_kernel(const float* __restrict__ low, long ld, int N, int H,
+                                                                int W, int Hm, int Wm, float sh, float sw, float zthr,
+                                                                uint8_t* __restrict__ mask, int Hf, int Wf, double ify,
+                                                                double ifx) {
+  const long total = (long)N * Hf * Wf;
+  for (long p = blockIdx.x * 256L + threadIdx.x; p < total; p += (long)gridDim.x * 256) {
+    const int n = (int)(p / ((long)Hf * Wf));
+    const int rem = (int)(p - (long)n * Hf * Wf);
+    const int yf = rem / Wf, xf = rem - yf * Wf;
+    mask[p] = (uint8_t)model_foreground(low + (long)n * H * W * ld, ld, H, W, nearest_src(yf, ify, Hm),
+                                        nearest_src(xf, ifx, Wm), sh, sw, zthr);
+  }
+}
+
 // The same mask by bands of kBandRows frame rows per block: the block classifies the model rows its band
 // maps to once (a frame 5.6x taller than the model repeats each model row ~6 times, and each model pixel
 // ~28 times over a 720x1280 frame), keeps the classes in LDS and writes the band's frame rows from them,
@@ -583,6 +611,20 @@ SEG_API int seg_argmax_nearest(const float* low, long ld, int N, int H, int W, i
   else
     hipLaunchKernelGGL(argmax_nearest_kernel, dim3(grid_for((long)N * Hf * Wf)), dim3(256), 0, stream, low, ld, N, H,
                        W, C, Hm, Wm, sh, sw, mask, Hf, Wf, ify, ifx);
+  SEG_RET_LAST();
+}
+
+// seg_argmax_nearest for a one-logit model: rows of ld floats whose lane 0 is the logit; mask = 1 where the
+// upsampled logit of the nearest model pixel is > zthr (strict: a tie or a NaN gives 0), else 0.
+SEG_API int seg_threshold_nearest(const float* low, long ld, int N, int H, int W, int Hm, int Wm, float zthr,
+                                  uint8_t* mask, int Hf, int Wf, hipStream_t stream) {
+  if ((ld & 3) || ld < 4 || N <= 0 || H <= 0 || W <= 0 || Hm <= 0 || Wm <= 0 || Hf <= 0 || Wf <= 0 || zthr != zthr)
+    return (int)hipErrorInvalidValue;
+  const float sh = Hm > 1 ? (float)(H - 1) / (float)(Hm - 1) : 0.f;
+  const float sw = Wm > 1 ? (float)(W - 1) / (float)(Wm - 1) : 0.f;
+  const double ify = 1.0 / ((double)Hf / Hm), ifx = 1.0 / ((double)Wf / Wm);
+  hipLaunchKernelGGL(threshold_nearest_kernel, dim3(grid_for((long)N * Hf * Wf)), dim3(256), 0, stream, low, ld, N, H,
+                     W, Hm, Wm, sh, sw, zthr, mask, Hf, Wf, ify, ifx);
   SEG_RET_LAST();
 }
 

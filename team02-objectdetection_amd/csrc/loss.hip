@@ -1,5 +1,5 @@
 // The fused segmentation losses: per-pixel criteria fused with the model's final align_corners=True
-// bilinear upsample.  Five kernel families share one file and one set of per-pixel helpers:
+// bilinear upsample.  Six kernel families share one file and one set of per-pixel helpers:
 //   seg_ce_*    nn.CrossEntropyLoss() as the reference applies it (main.py:99, src/train.py:37) to the model
 //               output, whose last op is final_upsample (src/unet.py:30,49): weight=None, ignore_index=-100,
 //               label_smoothing=0, labels int64.  loss = sum_{valid p} (logsumexp(z_p) - z_p[y_p]) / #valid,
@@ -8,6 +8,7 @@
 //   seg_sl_*    a focal term and soft Dice beside cross-entropy (seg_amd.SegLoss).
 //   seg_ohem_*  online hard example mining (seg_amd.OhemCELoss).
 //   seg_kd_*    knowledge distillation from a teacher's logits (seg_amd.DistillLoss).
+//   seg_bce_*   one logit per pixel: sigmoid cross-entropy, focal exponent and soft Dice (seg_amd.BinarySegLoss).
 // Each family's formulas stand above its kernels.
 //
 // The full-resolution logits z_p are never stored: each kernel recomputes them from the NHWC low-resolution
@@ -1546,4 +1547,237 @@ SEG_API int seg_low_logits_f32(const float* low, long ld, long rows, int C, floa
 SEG_API int seg_low_logits_f32_bf16io(const __bf16* low, long ld, long rows, int C, float* out, long ldo,
                                       hipStream_t stream) {
   return low_logits_impl(low, ld, rows, C, out, ldo, stream);
+}
+
+// ---- one logit per pixel: sigmoid cross-entropy with a focal exponent, plus soft Dice: seg_bce_* ----
+// (the criterion is seg_amd.BinarySegLoss).  C = 1; labels t_p in {0, 1}, anything else that is not ignore_index is
+// out of range.  Over the valid pixels V, with z_p the pixel's logit, s_p = sigmoid(z_p), pt_p = s_p where t_p = 1
+// else 1 - s_p, and w_p = pos_weight where t_p = 1 else 1:
+//   F    = sum_V w_p (1 - pt_p)^gamma (-log pt_p) / |V|
+//   I = sum_V s_p t_p,  S = sum_V s_p,  T = sum_V t_p,  U = S + T + smooth,  Dice = 1 - (2 I + smooth) / U
+//   loss = bce F + dice Dice    (a term whose coefficient is 0 is left out, so its 0/0 never reaches the loss).
+// One pass writes six partials per block [focal sum, #valid, #out-of-range, I, S, T]; the one-wave fp64 finalize
+// writes stats8 = [loss, #valid, #out-of-range, #valid, F, Dice, a, b] with the Dice gradient's two coefficients
+// a = 2 / U and b = (2 I + smooth) / U^2, so the gradient kernel needs no table:
+//   dz_p = (g bce / |V|) (t_p ? -1 : 1) w_p (1 - pt)^gamma ((1 - pt) + gamma pt (-log pt)) - g dice (a t_p - b) s (1 - s).
+// Numerical form: e = exp(-|z|) is the only exponential; s and 1 - s are 1 / (1 + e) and e / (1 + e) by the sign
+// of z (never 1.f - s), s (1 - s) their product, -log sigmoid(x) = max(-x, 0) + log1p(e); everything is finite for
+// any finite z, and (1 - pt)^gamma is exactly 0 where 1 - pt is (seg_sl_*'s rule).
+// The z of a pixel is lane 0 of full_res_logits<4>: the row's three pad lanes are loaded with it and never used.
+// The gradient is ONE fp32 per pixel, [N][Ho][Wo] -- at C = 1 the NCHW plane seg_upsample_bwd(nchw_grad = 1) reads --
+// in both maths: 4 B a pixel where a round4(C) row costs 16, and (the seg_ohem_* / seg_kd_* twins' reason) the
+// low-resolution gradient of the bf16io twin sums unrounded terms.
+namespace {
+
+constexpr int BCE_NP = 6;
+
+struct BceOpt {
+  float pos_weight;
+  float bce, dice;  // the two coefficients
+  float gamma;      // focal exponent
+  float smooth;     // dice_smooth
+};
+
+inline bool bce_opt_ok(const BceOpt& o) {
+  return std::isfinite(o.pos_weight) && std::isfinite(o.bce) && std::isfinite(o.dice) && std::isfinite(o.gamma) &&
+         std::isfinite(o.smooth) && o.pos_weight > 0.f && o.bce >= 0.f && o.dice >= 0.f &&
+         (o.bce > 0.f || o.dice > 0.f) && o.gamma >= 0.f && o.smooth > 0.f;
+}
+inline bool bce_geom_ok(long ld, int C) { return loss_geom_ok(ld, C) && C == 1; }
+
+// sigmoid(z), sigmoid(-z) and log1p(exp(-|z|)) from the one exponential
+struct Sig {
+  float s, c, l1p;
+};
+__device__ __forceinline__ Sig sigmoid_of(float z) {
+  const float e = expf(-fabsf(z));
+  const float inv = 1.f / (1.f + e);
+  const float big = inv, small = e * inv;
+  const bool pos = z >= 0.f;
+  return Sig{pos ? big : small, pos ? small : big, log1pf(e)};
+}
+
+template <typename T>
+__device__ __forceinline__ float one_logit(const T* __restrict__ low, long ld, int H, int W, const Pix& px, float sh,
+                                           float sw) {
+  float z[4];
+  full_res_logits<4, T>(low, ld, H, W, px.n, px.r, px.s, sh, sw, z);
+  return z[0];
+}
+
+template <typename T, bool EVAL>
+__global__ __launch_bounds__(256) void bce_up_loss_kernel(const T* __restrict__ low, long ld, int N, int H, int W,
+                                                          const long long* __restrict__ labels, int Ho, int Wo,
+                                                          float sh, float sw, int ignore_index,
+                                                          float* __restrict__ part, float zthr,
+                                                          unsigned long long* __restrict__ confusion, BceOpt o) {
+  __shared__ float red[4][BCE_NP];
+  __shared__ int hist[4];
+  if constexpr (EVAL) {
+    hist_clear(hist, 2);
+    __syncthreads();
+  }
+  const long total = (long)N * Ho * Wo;
+  const bool focal = o.gamma > 0.f;
+  float fsum = 0.f, cnt = 0.f, bad = 0.f, isum = 0.f, ssum = 0.f, tsum = 0.f;
+  for (long p = blockIdx.x * (long)blockDim.x + threadIdx.x; p < total; p += (long)gridDim.x * blockDim.x) {
+    const long long y = labels[p];
+    if (y == ignore_index) continue;
+    if (y < 0 || y > 1) {
+      bad += 1.f;
+      continue;
+    }
+    const bool fg = y == 1;
+    const float z = one_logit<T>(low, ld, H, W, pixel_of(p, Ho, Wo), sh, sw);
+    const Sig g = sigmoid_of(z);
+    const float nlp = fmaxf(fg ? -z : z, 0.f) + g.l1p;  // -log pt
+    const float omp = fg ? g.c : g.s;                   // 1 - pt
+    const float wy = fg ? o.pos_weight : 1.f;
+    float pw = 1.f;
+    if (focal) pw = omp > 0.f ? powf(omp, o.gamma) : 0.f;
+    fsum = __builtin_fmaf(wy * pw, nlp, fsum);
+    cnt += 1.f;
+    ssum += g.s;
+    isum += fg ? g.s : 0.f;
+    tsum += fg ? 1.f : 0.f;
+    if constexpr (EVAL) hist_count(hist, 2, (int)y, z > zthr ? 1 : 0);  // strict: a tie or a NaN is background
+  }
+  const float v[BCE_NP] = {fsum, cnt, bad, isum, ssum, tsum};
+  block_partials<BCE_NP>(v, red, part);
+  if constexpr (EVAL) hist_flush(hist, 2, confusion);
+}
+
+__global__ void bce_finalize_kernel(const float* __restrict__ part, int nblk, float bce, float dice, float smooth,
+                                    float* __restrict__ out) {
+  double t[BCE_NP];
+  column_sums_f64<BCE_NP>(part, nblk, BCE_NP, t);
+  if (threadIdx.x == 0) {
+    const double f = t[0], c = t[1], b = t[2], I = t[3], S = t[4], Tc = t[5];
+    const double F = f / c;  // 0/0 = nan when every pixel is ignored, as aten
+    const double U = S + Tc + (double)smooth, num = 2.0 * I + (double)smooth;
+    const double Dice = 1.0 - num / U;
+    double loss = 0.0;
+    if (bce > 0.f) loss += (double)bce * F;
+    if (dice > 0.f) loss += (double)dice * Dice;
+    out[0] = b > 0.0 ? __builtin_nanf("") : (float)loss;
+    out[1] = (float)c;
+    out[2] = (float)b;
+    out[3] = (float)c;
+    out[4] = (float)F;
+    out[5] = (float)Dice;
+    out[6] = (float)(2.0 / U);
+    out[7] = (float)(num / (U * U));
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void bce_up_grad_kernel(const T* __restrict__ low, long ld, int N, int H, int W,
+                                                          const long long* __restrict__ labels, int Ho, int Wo,
+                                                          float sh, float sw, int ignore_index,
+                                                          const float* __restrict__ gout,
+                                                          const float* __restrict__ stats, float* __restrict__ dhigh,
+                                                          BceOpt o) {
+  const long total = (long)N * Ho * Wo;
+  const bool poisoned = stats[2] > 0.f, has_bce = o.bce > 0.f, has_dice = o.dice > 0.f, focal = o.gamma > 0.f;
+  const float sce = poisoned ? __builtin_nanf("") : has_bce ? gout[0] * o.bce / stats[1] : 0.f;  // g bce / |V|
+  const float sdi = poisoned ? __builtin_nanf("") : gout[0] * o.dice;                             // g dice
+  const float a = stats[6], b = stats[7];
+  for (long p = blockIdx.x * (long)blockDim.x + threadIdx.x; p < total; p += (long)gridDim.x * blockDim.x) {
+    const long long y = labels[p];
+    if (y == ignore_index || y < 0 || y > 1) {
+      dhigh[p] = 0.f;
+      continue;
+    }
+    const bool fg = y == 1;
+    const float z = one_logit<T>(low, ld, H, W, pixel_of(p, Ho, Wo), sh, sw);
+    const Sig g = sigmoid_of(z);
+    const float omp = fg ? g.c : g.s, pt = fg ? g.s : g.c;
+    float fp = omp;  // (1 - pt)^gamma ((1 - pt) + gamma pt (-log pt))
+    if (focal) {
+      const float nlp = fmaxf(fg ? -z : z, 0.f) + g.l1p;
+      fp = omp > 0.f ? powf(omp, o.gamma) * __builtin_fmaf(o.gamma * pt, nlp, omp) : 0.f;
+    }
+    const float wy = fg ? o.pos_weight : 1.f;
+    float d = sce * (fg ? -(wy * fp) : wy * fp);
+    if (has_dice) d = __builtin_fmaf(sdi * (g.s * g.c), fg ? b - a : b, d);
+    dhigh[p] = d;
+  }
+}
+
+template <typename T, bool EVAL>
+int bce_loss_impl(const T* low, long ld, int N, int H, int W, int C, const long long* labels, int Ho, int Wo,
+                  int ignore_index, BceOpt o, float* work, float* out8, float zthr, long long* confusion,
+                  hipStream_t stream) {
+  if (!bce_geom_ok(ld, C) || (EVAL && !confusion) || !bce_opt_ok(o)) return (int)hipErrorInvalidValue;
+  const int nb = loss_blocks((long)N * Ho * Wo);
+  const UpScale up = up_scale(H, W, Ho, Wo);
+  hipLaunchKernelGGL((bce_up_loss_kernel<T, EVAL>), dim3(nb), dim3(256), 0, stream, low, ld, N, H, W, labels, Ho, Wo,
+                     up.sh, up.sw, ignore_index, work, zthr, (unsigned long long*)confusion, o);
+  hipLaunchKernelGGL(bce_finalize_kernel, dim3(1), dim3(64), 0, stream, work, nb, o.bce, o.dice, o.smooth, out8);
+  SEG_RET_LAST();
+}
+
+template <typename T>
+int bce_grad_impl(const T* low, long ld, int N, int H, int W, int C, const long long* labels, int Ho, int Wo,
+                  int ignore_index, BceOpt o, const float* grad_out, const float* stats, float* dhigh,
+                  hipStream_t stream) {
+  if (!bce_geom_ok(ld, C) || !bce_opt_ok(o)) return (int)hipErrorInvalidValue;
+  const UpScale up = up_scale(H, W, Ho, Wo);
+  hipLaunchKernelGGL((bce_up_grad_kernel<T>), dim3(grad_blocks((long)N * Ho * Wo)), dim3(256), 0, stream, low, ld, N,
+                     H, W, labels, Ho, Wo, up.sh, up.sw, ignore_index, grad_out, stats, dhigh, o);
+  SEG_RET_LAST();
+}
+
+}  // namespace
+
+// stats8 = [loss, #valid, #out-of-range labels, #valid, F, Dice, a, b]; `work` >= seg_bce_workspace_floats(N*Ho*Wo).
+SEG_API long seg_bce_workspace_floats(long pixels) { return (long)BCE_NP * loss_blocks(pixels); }
+
+SEG_API int seg_bce_upsample_loss(const float* low, long ld, int N, int H, int W, int C, const long long* labels,
+                                  int Ho, int Wo, int ignore_index, float pos_weight, float bce, float dice,
+                                  float focal_gamma, float dice_smooth, float* work, float* stats8,
+                                  hipStream_t stream) {
+  return bce_loss_impl<float, false>(low, ld, N, H, W, C, labels, Ho, Wo, ignore_index,
+                                     BceOpt{pos_weight, bce, dice, focal_gamma, dice_smooth}, work, stats8, 0.f,
+                                     nullptr, stream);
+}
+SEG_API int seg_bce_upsample_loss_bf16io(const __bf16* low, long ld, int N, int H, int W, int C,
+                                         const long long* labels, int Ho, int Wo, int ignore_index, float pos_weight,
+                                         float bce, float dice, float focal_gamma, float dice_smooth, float* work,
+                                         float* stats8, hipStream_t stream) {
+  return bce_loss_impl<__bf16, false>(low, ld, N, H, W, C, labels, Ho, Wo, ignore_index,
+                                      BceOpt{pos_weight, bce, dice, focal_gamma, dice_smooth}, work, stats8, 0.f,
+                                      nullptr, stream);
+}
+// Validation: the same loss and stats, and confusion[t * 2 + (z > zthr)] += 1 per valid pixel (int64 [2][2]).
+SEG_API int seg_bce_upsample_eval(const float* low, long ld, int N, int H, int W, int C, const long long* labels,
+                                  int Ho, int Wo, int ignore_index, float pos_weight, float bce, float dice,
+                                  float focal_gamma, float dice_smooth, float* work, float* stats8, float zthr,
+                                  long long* confusion, hipStream_t stream) {
+  return bce_loss_impl<float, true>(low, ld, N, H, W, C, labels, Ho, Wo, ignore_index,
+                                    BceOpt{pos_weight, bce, dice, focal_gamma, dice_smooth}, work, stats8, zthr,
+                                    confusion, stream);
+}
+SEG_API int seg_bce_upsample_eval_bf16io(const __bf16* low, long ld, int N, int H, int W, int C,
+                                         const long long* labels, int Ho, int Wo, int ignore_index, float pos_weight,
+                                         float bce, float dice, float focal_gamma, float dice_smooth, float* work,
+                                         float* stats8, float zthr, long long* confusion, hipStream_t stream) {
+  return bce_loss_impl<__bf16, true>(low, ld, N, H, W, C, labels, Ho, Wo, ignore_index,
+                                     BceOpt{pos_weight, bce, dice, focal_gamma, dice_smooth}, work, stats8, zthr,
+                                     confusion, stream);
+}
+// dhigh: fp32 [N][Ho][Wo] in both maths; follow with seg_upsample_bwd(nchw_grad = 1, ac = 2).
+SEG_API int seg_bce_upsample_grad(const float* low, long ld, int N, int H, int W, int C, const long long* labels,
+                                  int Ho, int Wo, int ignore_index, float pos_weight, float bce, float dice,
+                                  float focal_gamma, const float* grad_out, const float* stats8, float* dhigh,
+                                  hipStream_t stream) {
+  return bce_grad_impl(low, ld, N, H, W, C, labels, Ho, Wo, ignore_index,
+                       BceOpt{pos_weight, bce, dice, focal_gamma, 1.f}, grad_out, stats8, dhigh, stream);
+}
+SEG_API int seg_bce_upsample_grad_bf16io(const __bf16* low, long ld, int N, int H, int W, int C,
+                                         const long long* labels, int Ho, int Wo, int ignore_index, float pos_weight,
+                                         float bce, float dice, float focal_gamma, const float* grad_out,
+                                         const float* stats8, float* dhigh, hipStream_t stream) {
+  return bce_grad_impl(low, ld, N, H, W, C, labels, Ho, Wo, ignore_index,
+                       BceOpt{pos_weight, bce, dice, focal_gamma, 1.f}, grad_out, stats8, dhigh, stream);
 }

@@ -8,6 +8,8 @@ Public surface (drop-in for the reference's src/unet.py and src/train.py):
     class_weights                         (nn.CrossEntropyLoss(weight=...) from pixel counts or a confusion matrix)
     SegLoss                               (cross-entropy with a focal exponent plus soft Dice, fused like CE)
     OhemCELoss                            (cross-entropy with online hard example mining, fused like CE)
+    BinarySegLoss, binary_summary         (one-logit models: sigmoid BCE / focal / Dice, fused like CE; validation
+                                           thresholds the logit and reports precision, recall and F1)
     DistillLoss                           (knowledge distillation: CE plus the tempered KL to a teacher's logits,
                                            both models' final upsamples fused into the loss kernels)
     Adam                                  (main.py:100's optimizer, one-launch HIP step)
@@ -28,8 +30,8 @@ All compute runs in libsegamd.so (HIP, gfx950); see include/segamd.h.
 """
 from .unet import MobileNetV2UNet, UNet, LightUNet, double_conv, inconv, down, up, outconv  # noqa: F401
 from .train import train_model, train_one_epoch, validate  # noqa: F401
-from .metrics import class_weights, summarize  # noqa: F401
-from .losses import DistillLoss, OhemCELoss, SegLoss  # noqa: F401
+from .metrics import binary_summary, class_weights, summarize  # noqa: F401
+from .losses import BinarySegLoss, DistillLoss, OhemCELoss, SegLoss  # noqa: F401
 from .detinit import deterministic_init, synthetic_batch  # noqa: F401
 from .data import CombinedLaneDataset, DistributedWeightedSampler, reference_sample_weights  # noqa: F401
 from .infer import Predictor, preprocess_image  # noqa: F401
@@ -42,7 +44,7 @@ from .freeze import freeze, unfreeze, frozen_modules  # noqa: F401
 
 __all__ = ["MobileNetV2UNet", "UNet", "LightUNet", "double_conv", "inconv", "down", "up", "outconv",
            "train_model", "train_one_epoch", "validate", "summarize", "class_weights", "SegLoss", "OhemCELoss",
-           "DistillLoss",
+           "DistillLoss", "BinarySegLoss", "binary_summary",
            "deterministic_init",
            "synthetic_batch",
            "CombinedLaneDataset", "DistributedWeightedSampler", "reference_sample_weights",

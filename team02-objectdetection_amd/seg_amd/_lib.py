@@ -104,9 +104,14 @@ PROTOTYPES = {
     "seg_kd_upsample_grad": (_I, [_V, _L, _I, _I, _I, _I, _V, _L, _I, _I, _V, _I, _I, _I, _V, _F, _F, _F, _I, _V, _V,
                                   _V, _L, _V]),
     "seg_low_logits_f32": (_I, [_V, _L, _L, _I, _V, _L, _V]),
+    "seg_bce_workspace_floats": (_L, [_L]),
+    "seg_bce_upsample_loss": (_I, [_V, _L, _I, _I, _I, _I, _V, _I, _I, _I, _F, _F, _F, _F, _F, _V, _V, _V]),
+    "seg_bce_upsample_eval": (_I, [_V, _L, _I, _I, _I, _I, _V, _I, _I, _I, _F, _F, _F, _F, _F, _V, _V, _F, _V, _V]),
+    "seg_bce_upsample_grad": (_I, [_V, _L, _I, _I, _I, _I, _V, _I, _I, _I, _F, _F, _F, _F, _V, _V, _V, _V]),
     "seg_bn_fold_batch": (_I, [_V, _I, _L, _V]),
     "seg_preprocess_bgr": (_I, [_V, _I, _I, _I, _L, _V, _I, _I, _I, _F, _F, _F, _F, _F, _F, _V]),
     "seg_argmax_nearest": (_I, [_V, _L, _I, _I, _I, _I, _I, _I, _V, _I, _I, _V]),
+    "seg_threshold_nearest": (_I, [_V, _L, _I, _I, _I, _I, _I, _F, _V, _I, _I, _V]),
     "seg_temporal_argmax_nearest": (_I, [_V, _L, _I, _I, _I, _I, _I, _I, _V, _I, _V, _F, _F, _I, _V, _V, _I, _I, _V]),
     # test-time augmentation (csrc/tta.hip, csrc/infer.hip, seg_amd/tta.py)
     "seg_tta_view_nchw": (_I, [_V, _I, _I, _I, _I, _V, _I, _I, _I, _V]),
@@ -181,7 +186,8 @@ for _n in ("seg_add", "seg_bn_stats", "seg_bn_apply", "seg_bn_backward", "seg_bn
            "seg_dw_wgrad", "seg_ce_upsample_loss", "seg_ce_upsample_grad", "seg_ce_upsample_eval", "seg_cew_upsample_loss",
            "seg_cew_upsample_grad", "seg_cew_upsample_eval", "seg_sl_upsample_loss", "seg_sl_upsample_grad",
            "seg_sl_upsample_eval", "seg_ohem_upsample_loss", "seg_ohem_upsample_eval", "seg_kd_upsample_loss",
-           "seg_kd_upsample_grad", "seg_low_logits_f32",
+           "seg_kd_upsample_grad", "seg_low_logits_f32", "seg_bce_upsample_loss", "seg_bce_upsample_eval",
+           "seg_bce_upsample_grad",  # the gradient is the fp32 plane in both maths
            "seg_upsample_fwd",
            "seg_upsample_bwd", "seg_upsample_to_nchw", "seg_nchw_to_nhwc", "seg_maxpool2_fwd", "seg_maxpool2_bwd"):
     PROTOTYPES[_n + "_bf16io"] = PROTOTYPES[_n]

@@ -347,7 +347,8 @@ class DataParallel(nn.Module):
         per rank in the same way.  So is seg_amd.OhemCELoss's selection (ohem_thresh, ohem_min_kept): each
         rank mines the hard pixels of its own shard.  A seg_amd.DistillLoss's kd, kd_temperature, kd_ignored and
         teacher_logits pass through in the same way: each rank distils its own shard (the teacher is no part of the
-        wrapped module, so nothing of it is all-reduced)."""
+        wrapped module, so nothing of it is all-reduced).  So do a seg_amd.BinarySegLoss's binary and pos_weight (and
+        threshold in forward_metrics): its Dice sums are per rank too."""
         self._pre(x)
         return self.module.forward_loss(x, target, ignore_index, weight, label_smoothing, reduction, **seg_loss)
 

@@ -1674,6 +1674,17 @@ class Distill(NamedTuple):
     Wt: int = 0
 
 
+class Binary(NamedTuple):
+    """A seg_amd.BinarySegLoss's scalars in loss_options' fourth slot: the seg_bce_* kernels.  threshold is read by
+    "metrics" mode only (the confusion matrix's z > zthr)."""
+    bce: float
+    dice: float
+    focal_gamma: float
+    dice_smooth: float
+    pos_weight: float
+    threshold: float = 0.5
+
+
 def check_teacher_logits(teacher_logits, N, C, device):
     """(Ht, Wt) of a teacher's low-resolution logits as the seg_kd_* kernels take them: a contiguous float32
     [N, Ht, Wt, round4(C)] tensor on `device` (model.forward_low_logits' result); ValueError otherwise."""
@@ -1692,7 +1703,8 @@ def check_teacher_logits(teacher_logits, N, C, device):
 
 
 def loss_options(weight, label_smoothing, reduction, C, device, ce=1.0, dice=0.0, focal_gamma=0.0, dice_smooth=1.0,
-                 ohem_thresh=None, ohem_min_kept=None, kd=0.0, kd_temperature=1.0, kd_ignored=True):
+                 ohem_thresh=None, ohem_min_kept=None, kd=0.0, kd_temperature=1.0, kd_ignored=True, binary=False,
+                 pos_weight=1.0, threshold=0.5):
     """The checked (weight, label_smoothing, reduction, sl) of a fused loss over C classes on `device`; ValueError
     for what the kernels do not take.  nn.CrossEntropyLoss's options for class-index targets, reduction "none" apart,
     and seg_amd.SegLoss's: sl is None for plain cross-entropy (ce = 1, no Dice term, no focal exponent: the seg_ce_* /
@@ -1700,8 +1712,19 @@ def loss_options(weight, label_smoothing, reduction, C, device, ce=1.0, dice=0.0
     With ohem_thresh / ohem_min_kept (a seg_amd.OhemCELoss's thresh and min_kept, both or neither) sl is an Ohem: the
     seg_ohem_* kernels, which take class weights and nothing else.  With kd != 0 (a seg_amd.DistillLoss's kd,
     temperature and kd_ignored) sl is a Distill: the seg_kd_* kernels, class weights and ce beside them and nothing
-    else; the teacher tensor's geometry is filled in by the caller (check_teacher_logits)."""
-    from .losses import check_distill_options, check_ohem_options, check_seg_loss_options
+    else; the teacher tensor's geometry is filled in by the caller (check_teacher_logits).  With binary=True (a
+    seg_amd.BinarySegLoss: ce is its bce coefficient, dice, focal_gamma and dice_smooth keep their names, pos_weight
+    and threshold are its own) sl is a Binary: the seg_bce_* kernels over a model whose logits have one channel; class
+    weights, label smoothing, any reduction but the mean, OHEM and kd are then a ValueError."""
+    from .losses import (check_binary_combination, check_binary_options, check_distill_options, check_ohem_options,
+                         check_seg_loss_options)
+    if binary:
+        check_binary_combination(weight, label_smoothing, reduction, ohem_thresh, ohem_min_kept, kd)
+        if C != 1:
+            raise ValueError(f"binary=True needs a model with one output channel, this one has {C}")
+        bce, dice, focal_gamma, pos_weight, dice_smooth, threshold = check_binary_options(
+            ce, dice, focal_gamma, pos_weight, dice_smooth, threshold)
+        return None, 0.0, "mean", Binary(bce, dice, focal_gamma, dice_smooth, pos_weight, threshold)
     if kd != 0.0:
         sl = Distill(*check_distill_options(ce, kd, kd_temperature, label_smoothing, reduction, dice, focal_gamma,
                                             ohem_thresh, ohem_min_kept), bool(kd_ignored))
@@ -1745,6 +1768,8 @@ class LossFamily(NamedTuple):
     ac: int       # of the seg_upsample_bwd behind the gradient: 2 = the transpose of the kd kernels' own blend (lin_ac)
     fwd: object
     grad: object
+    plane: bool = False  # the gradient is fp32 NCHW in BOTH maths, under the family's plain _grad name (no ldh)
+    ev: object = None    # what an _eval call puts between the stats and the confusion matrix (bce: zthr)
 
 
 def _kd_head(a, o):  # the teacher's rows sit before the labels
@@ -1755,7 +1780,17 @@ def _kd_opts(a, o):
     return (a.w, o.ce, o.kd, o.temperature, int(o.kd_ignored))
 
 
-# opt: cew (eps, reduction), sl (eps, ce, dice, focal_gamma, dice_smooth), ohem (tau, min_kept), kd a Distill
+def _bce_opts(o):
+    return (o.pos_weight, o.bce, o.dice, o.focal_gamma)
+
+
+def _bce_zthr(o):
+    from .losses import logit_threshold
+    return (logit_threshold(o.threshold),)
+
+
+# opt: cew (eps, reduction), sl (eps, ce, dice, focal_gamma, dice_smooth), ohem (tau, min_kept), kd a Distill,
+# bce a Binary
 LOSS_FAMILIES = {f.stem: f for f in (
     LossFamily("ce", 3, True, None, 1,
                lambda a, o: a.head + a.labels + a.out,
@@ -1772,6 +1807,11 @@ LOSS_FAMILIES = {f.stem: f for f in (
     LossFamily("kd", 6, False, "_nchw", 2,
                lambda a, o: _kd_head(a, o) + _kd_opts(a, o) + a.out,
                lambda a, o: _kd_head(a, o) + _kd_opts(a, o) + a.out),
+    # one logit: stats end in the Dice gradient's a and b; one float of gradient per pixel, so the plane always
+    LossFamily("bce", 8, True, None, 2,
+               lambda a, o: a.head + a.labels + _bce_opts(o) + (o.dice_smooth,) + a.out,
+               lambda a, o: a.head + a.labels + _bce_opts(o) + a.out,
+               True, _bce_zthr),
 )}
 
 
@@ -1807,13 +1847,18 @@ def _loss_forward(run, t, ignore_index, confusion=None, weight=None, label_smoot
     kernel reads back.
     sl = Distill(ce, kd, temperature, kd_ignored, Ht, Wt) of a seg_amd.DistillLoss: the seg_kd_* kernels over
     run.teacher (fp32 NHWC rows [N, Ht, Wt, round4(C)], a tape external like the class weights), stats = [loss, D,
-    #bad labels, #valid, CE, KD]."""
+    #bad labels, #valid, CE, KD].
+    sl = Binary(bce, dice, focal_gamma, dice_smooth, pos_weight, threshold) of a seg_amd.BinarySegLoss: the seg_bce_*
+    kernels over the model's one logit, stats = [loss, #valid, #bad labels, #valid, F, Dice, a, b]; confusion is then
+    int64 [2, 2], confusion[label, z > zthr]."""
     prog, s = run.prog, run.stream
     Ho, Wo = prog.out_hw
     pixels = prog.N * Ho * Wo
     run.target, run.weight = t, weight
     if isinstance(sl, Distill):
         fam, opt = LOSS_FAMILIES["kd"], sl
+    elif isinstance(sl, Binary):
+        fam, opt = LOSS_FAMILIES["bce"], sl
     elif isinstance(sl, Ohem):
         from .losses import resolve_min_kept
         # tau: float64 here, a float in the kernels
@@ -1834,7 +1879,8 @@ def _loss_forward(run, t, ignore_index, confusion=None, weight=None, label_smoot
     if confusion is None:
         run.call(run.k(f"seg_{fam.stem}_upsample_loss"), *args, s)
     else:
-        run.call(run.k(f"seg_{fam.stem}_upsample_eval"), *args, confusion.data_ptr(), s)
+        extra = fam.ev(opt) if fam.ev is not None else ()
+        run.call(run.k(f"seg_{fam.stem}_upsample_eval"), *args, *extra, confusion.data_ptr(), s)
     return run.stats
 
 
@@ -1845,15 +1891,15 @@ def _loss_backward(run, g, ignore_index):
     Ho, Wo = prog.out_hw
     fam, opt = run.loss.fam, run.loss.opt
     # the bf16io twins of ohem and kd: the full-resolution gradient in fp32 NCHW, as behind the model's logits (bf16
-    # rows would round every term of the low-resolution gradient's sums)
-    nchw = run.io and fam.nchw is not None
+    # rows would round every term of the low-resolution gradient's sums); bce: the plane in both maths (fam.plane)
+    nchw = fam.plane or (run.io and fam.nchw is not None)
     if nchw:
         dhigh = torch.empty(max(N * lo.C * Ho * Wo, 1), device=run.device, dtype=torch.float32)
     else:
         dhigh = torch.empty(max(N * Ho * Wo * lo.ld, 1), device=run.device, dtype=run.store)
     run.keep.append(dhigh)
     ldh = () if nchw else (lo.ld,)
-    run.call(run.k(f"seg_{fam.stem}_upsample_grad") + (fam.nchw if nchw else ""),
+    run.call(run.k(f"seg_{fam.stem}_upsample_grad") + (fam.nchw if nchw and not fam.plane else ""),
              *fam.grad(_loss_args(run, ignore_index, g), opt), dhigh.data_ptr(), *ldh, s)
     run.call(run.k("seg_upsample_bwd"), dhigh.data_ptr(), 0 if nchw else lo.ld, int(nchw), N, Ho, Wo, lo.C,
              run.gptr(lo), lo.ld, lo.H, lo.W, fam.ac, 0, s)
@@ -2220,18 +2266,26 @@ def run_loss(model, x: torch.Tensor, target: torch.Tensor, ignore_index: int = I
              label_smoothing: float = 0.0, reduction: str = "mean", ce: float = 1.0, dice: float = 0.0,
              focal_gamma: float = 0.0, dice_smooth: float = 1.0, ohem_thresh=None,
              ohem_min_kept=None, kd: float = 0.0, kd_temperature: float = 1.0, kd_ignored: bool = True,
-             teacher_logits=None) -> torch.Tensor:
+             teacher_logits=None, binary: bool = False, pos_weight: float = 1.0) -> torch.Tensor:
     """nn.CrossEntropyLoss(weight, ignore_index=..., reduction=..., label_smoothing=...)(model(x), target),
     seg_amd.SegLoss(ce, dice, focal_gamma, weight, ...)(model(x), target) or seg_amd.OhemCELoss(ohem_thresh,
     ohem_min_kept, weight, ...)(model(x), target), with the loss fused into the final upsample
     (csrc/loss.hip); the options are checked by loss_options (ValueError).  With kd > 0 and teacher_logits (a teacher's
     forward_low_logits(x): float32 [N, Ht, Wt, round4(C)]) the loss is seg_amd.DistillLoss(teacher, ce, kd,
     kd_temperature, weight, ignore_index, kd_ignored)'s, the teacher's logits upsampled inside the same kernels
-    (seg_kd_*); the tensor is read by the forward and by the backward and may be a new one every step."""
+    (seg_kd_*); the tensor is read by the forward and by the backward and may be a new one every step.  With
+    binary=True the loss is seg_amd.BinarySegLoss(bce=ce, dice, focal_gamma, pos_weight, ignore_index, dice_smooth)'s
+    over the model's one logit (seg_bce_*); the target may then be [N, 1, Ho, Wo] and of any integer or bool dtype."""
     _check_input(x)
     sync = model.__dict__.get("_segamd_sync")
     opts = (weight, label_smoothing, reduction, (ce, dice, focal_gamma, dice_smooth, ohem_thresh, ohem_min_kept))
-    if kd != 0.0 or teacher_logits is not None:  # the defaults keep the tuple (and the code path) they always had
+    if binary:
+        from .losses import binary_target
+        if teacher_logits is not None:
+            raise ValueError("binary=True does not combine with distillation")
+        target = binary_target(None, target)
+        opts = (*opts[:3], (*opts[3], kd, kd_temperature, kd_ignored, True, pos_weight))
+    elif kd != 0.0 or teacher_logits is not None:  # the defaults keep the tuple (and the code path) they always had
         opts = (*opts[:3], (*opts[3], kd, kd_temperature, kd_ignored), teacher_logits)
     return _SegFunction.apply(model, "loss", x, target, ignore_index, sync, opts, *_params_for(model, x))
 
@@ -2253,12 +2307,14 @@ def run_low_logits(model, x: torch.Tensor) -> torch.Tensor:
 def run_metrics(model, x: torch.Tensor, target: torch.Tensor, confusion: torch.Tensor,
                 ignore_index: int = IGNORE_INDEX, weight=None, label_smoothing: float = 0.0,
                 reduction: str = "mean", ce: float = 1.0, dice: float = 0.0, focal_gamma: float = 0.0,
-                dice_smooth: float = 1.0, ohem_thresh=None, ohem_min_kept=None) -> torch.Tensor:
+                dice_smooth: float = 1.0, ohem_thresh=None, ohem_min_kept=None, binary: bool = False,
+                pos_weight: float = 1.0, threshold: float = 0.5) -> torch.Tensor:
     """Validation forward: the fused loss of run_loss, and in the same kernel
     confusion[label, argmax of the full-resolution logits] += 1 for every valid pixel
     (csrc/loss.hip: seg_ce_upsample_eval, seg_cew_upsample_eval with loss options, seg_sl_upsample_eval for a
     SegLoss's Dice / focal terms or seg_ohem_upsample_eval for an OhemCELoss -- they change the returned loss only,
-    never the matrix, which counts every valid pixel).
+    never the matrix, which counts every valid pixel).  With binary=True (a seg_amd.BinarySegLoss over a one-logit
+    model: seg_bce_upsample_eval) the matrix is int64 [2, 2], confusion[label, z > log(threshold / (1 - threshold))].
     A forward tape only: no gradient is ever built, so
     DataParallel's buckets are not involved (sync is None).  Plans are keyed by model.training
     like the others: eval() uses the running statistics, train() the batch's."""
@@ -2268,16 +2324,24 @@ def run_metrics(model, x: torch.Tensor, target: torch.Tensor, confusion: torch.T
     prog = get_program(model, N, H, W)
     Ho, Wo = prog.out_hw
     C = prog.logits.C
+    if binary:
+        from .losses import binary_target
+        target = binary_target(None, target)
     t = target.contiguous()
     if t.dtype != torch.int64 or tuple(t.shape) != (N, Ho, Wo) or t.device != x.device:
         raise ValueError(f"target must be int64 [{N},{Ho},{Wo}] on {x.device}, got {tuple(t.shape)} {t.dtype} "
                          f"on {t.device}")
-    if (confusion.dtype != torch.int64 or tuple(confusion.shape) != (C, C) or confusion.device != x.device
+    K = 2 if binary else C  # a one-logit model's matrix is [label, z > zthr]
+    if (confusion.dtype != torch.int64 or tuple(confusion.shape) != (K, K) or confusion.device != x.device
             or not confusion.is_contiguous()):
-        raise ValueError(f"confusion must be a contiguous int64 [{C},{C}] tensor on {x.device}, got "
+        raise ValueError(f"confusion must be a contiguous int64 [{K},{K}] tensor on {x.device}, got "
                          f"{tuple(confusion.shape)} {confusion.dtype} on {confusion.device}")
-    opts = loss_options(weight, label_smoothing, reduction, C, x.device, ce, dice, focal_gamma, dice_smooth,
-                        ohem_thresh, ohem_min_kept)
+    if binary:
+        opts = loss_options(weight, label_smoothing, reduction, C, x.device, ce, dice, focal_gamma, dice_smooth,
+                            ohem_thresh, ohem_min_kept, binary=True, pos_weight=pos_weight, threshold=threshold)
+    else:
+        opts = loss_options(weight, label_smoothing, reduction, C, x.device, ce, dice, focal_gamma, dice_smooth,
+                            ohem_thresh, ohem_min_kept)
     plan = _plan(model, prog, "metrics", ignore_index, None, False, x.device, opts)
     plan.forward(x, t, confusion, opts[0])
     return _publish_stats(model, plan.run.stats)

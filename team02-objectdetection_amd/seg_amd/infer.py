@@ -115,12 +115,27 @@ class Predictor:
     tta_batch=False runs every view as a batch-1 forward of its own instead -- what math="f16" always does: its
     fused inverted-residual launches are batch-1 routes, so tta_batch=True is a ValueError there.  tta together
     with temporal is a ValueError.
+
+    threshold (a probability in (0, 1); None: the argmax path, unchanged) classifies a one-channel model: the mask is
+    1 where the upsampled logit is > log(threshold / (1 - threshold)) -- strictly, so a tie or a NaN logit is
+    background -- else 0 (seg_threshold_nearest in place of seg_argmax_nearest, inside the graph too).  The mask feeds
+    the overlay unchanged: its road = (cls == 1) is the model's foreground.  A model with more channels, or threshold
+    together with temporal, min_confidence or tta, is a ValueError.
     """
 
     def __init__(self, model, frame_hw=(720, 1280), target_size=(256, 128), graph: bool = True, math: str = "f32",
                  overlay=False, temporal: float | None = None, min_confidence: float = 0.0, fallback_class: int = 0,
-                 tta=None, tta_batch: bool | None = None):
+                 tta=None, tta_batch: bool | None = None, threshold: float | None = None):
         temporal_options(temporal, min_confidence, fallback_class)  # bad values: ValueError before anything else
+        self.zthr = None  # None: every line of the argmax path as it always was
+        if threshold is not None:
+            from .losses import logit_threshold
+            if not isinstance(threshold, numbers.Real) or isinstance(threshold, bool):
+                raise ValueError(f"Predictor threshold must be None or a probability in (0, 1), got {threshold!r}")
+            self.zthr = logit_threshold(threshold)
+            if temporal is not None or min_confidence != 0 or tta is not None:
+                raise ValueError("Predictor threshold cannot be combined with temporal, min_confidence or tta: "
+                                 "smoothing or ensembling a one-logit model is not implemented")
         from .tta import as_tta
         self.tta = as_tta(tta)
         if self.tta is not None and temporal is not None:
@@ -155,7 +170,9 @@ class Predictor:
             same = [g[1] for g in self._tta_groups if (g[1].image.H, g[1].image.W) == (self.H, self.W)]
             self.prog = same[0] if same else get_program(model, 1, self.H, self.W, math)
         self.classes = self.prog.logits.C
-        self.temporal = temporal_options(temporal, min_confidence, fallback_class, self.classes)
+        if self.zthr is not None and self.classes != 1:
+            raise ValueError(f"Predictor threshold needs a model with one output channel, this one has {self.classes}")
+        self.temporal =temporal_options(temporal, min_confidence, fallback_class, self.classes)
         if self.tta is not None and self.temporal is None:
             self.temporal = (1.0, 0.0, 0)  # the state, labels and readers of the smoothing path; no threshold
         if self.temporal is not None:
@@ -247,7 +264,10 @@ class Predictor:
             rt.forward_folded()
         lo = prog.logits
         Ho, Wo = prog.out_hw
-        if self.temporal is None:
+        if self.zthr is not None:  # a one-logit model: the mask {0, 1} is z > zthr, the overlay's road its foreground
+            call("seg_threshold_nearest", rt.ptr(lo), lo.ld, 1, lo.H, lo.W, Ho, Wo, self.zthr, self.mask.data_ptr(),
+                 self.Hf, self.Wf, s)
+        elif self.temporal is None:
             call("seg_argmax_nearest", rt.ptr(lo), lo.ld, 1, lo.H, lo.W, lo.C, Ho, Wo, self.mask.data_ptr(), self.Hf,
                  self.Wf, s)
         else:

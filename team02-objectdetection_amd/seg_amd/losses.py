@@ -26,6 +26,10 @@ fused kernels are csrc/loss.hip's seg_ohem_*.
 DistillLoss (below) is pixel-wise knowledge distillation: cross-entropy plus T^2 KL(softmax(teacher / T) ||
 softmax(student / T)) against a second model's logits.  Its class docstring has the definition; the fused kernels are
 csrc/loss.hip's seg_kd_*.
+
+BinarySegLoss (below) is the sigmoid loss of a one-logit model: binary cross-entropy with pos_weight and a focal
+exponent, plus the foreground's soft Dice; its threshold is what validation and inference cut the logit at.  Its
+class docstring has the definition; the fused kernels are csrc/loss.hip's seg_bce_*.
 """
 from __future__ import annotations
 
@@ -208,11 +212,118 @@ def distill_loss_terms(logits, teacher_logits, target, ce=1.0, kd=1.0, temperatu
     return loss, hard, soft
 
 
+def check_binary_options(bce, dice, focal_gamma, pos_weight, dice_smooth, threshold=0.5):
+    """(bce, dice, focal_gamma, pos_weight, dice_smooth, threshold) as floats; ValueError for what BinarySegLoss's
+    definition excludes."""
+    bce, dice, gamma, pw, smooth, thr = (float(bce), float(dice), float(focal_gamma), float(pos_weight),
+                                         float(dice_smooth), float(threshold))
+    for name, v in (("bce", bce), ("dice", dice), ("focal_gamma", gamma)):
+        if not (math.isfinite(v) and v >= 0.0):
+            raise ValueError(f"{name} must be a finite number >= 0, got {v!r}")
+    if bce == 0.0 and dice == 0.0:
+        raise ValueError("bce and dice must not both be 0")
+    if not (math.isfinite(pw) and pw > 0.0):
+        raise ValueError(f"pos_weight must be a finite number > 0, got {pw!r}")
+    if not (math.isfinite(smooth) and smooth > 0.0):
+        raise ValueError(f"dice_smooth must be a finite number > 0, got {smooth!r}")
+    if not 0.0 < thr < 1.0:
+        raise ValueError(f"threshold must be a probability in (0, 1), got {thr!r}")
+    return bce, dice, gamma, pw, smooth, thr
+
+
+def check_binary_combination(weight=None, label_smoothing=0.0, reduction="mean", ohem_thresh=None,
+                             ohem_min_kept=None, kd=0.0):
+    """ValueError for what binary=True does not combine with: class weights (pos_weight is the binary loss's),
+    label smoothing, any reduction but the mean, online hard example mining and distillation."""
+    if weight is not None:
+        raise ValueError("binary=True takes pos_weight, not class weights")
+    if float(label_smoothing) != 0.0:
+        raise ValueError("binary=True is not defined with label smoothing")
+    if reduction != "mean":
+        raise ValueError(f"binary=True is defined for reduction 'mean' only, got {reduction!r}")
+    if ohem_thresh is not None or ohem_min_kept is not None:
+        raise ValueError("binary=True does not combine with online hard example mining")
+    if float(kd) != 0.0:
+        raise ValueError("binary=True does not combine with distillation")
+
+
+def logit_threshold(threshold: float) -> float:
+    """zthr = log(threshold / (1 - threshold)) in float64, cast to float32: the prediction is 1 iff z > zthr, on the
+    CPU and in the kernels (seg_bce_upsample_eval, seg_threshold_nearest) alike."""
+    thr = float(threshold)
+    if not 0.0 < thr < 1.0:
+        raise ValueError(f"threshold must be a probability in (0, 1), got {threshold!r}")
+    return float(torch.tensor(math.log(thr / (1.0 - thr)), dtype=torch.float64).to(torch.float32))
+
+
+def binary_target(logits, target):
+    """BinarySegLoss's target as an int64 [N, H, W] class-index mask: [N, 1, H, W] is squeezed, bool and the other
+    integer dtypes are converted with one torch op; a floating-point target is a TypeError (soft labels are
+    nn.BCEWithLogitsLoss's, on the logits path)."""
+    if not isinstance(target, torch.Tensor) or target.is_floating_point() or target.is_complex():
+        what = target.dtype if isinstance(target, torch.Tensor) else type(target).__name__
+        raise TypeError(f"BinarySegLoss takes class-index targets (an integer or bool mask of 0 / 1 / ignore_index), "
+                        f"got {what}; soft labels are nn.BCEWithLogitsLoss's")
+    if target.dim() == 4 and target.shape[1] == 1:
+        target = target[:, 0]
+    if target.dtype != torch.int64:
+        target = target.to(torch.int64)
+    return target
+
+
+def binary_loss_terms(logits, target, bce=1.0, dice=0.0, focal_gamma=0.0, pos_weight=1.0, ignore_index=-100,
+                      dice_smooth=1.0):
+    """(loss, F, Dice) of BinarySegLoss for `logits` [N, 1, H, W] and a class-index `target` [N, H, W] or
+    [N, 1, H, W] with values in {0, 1, ignore_index}, in torch ops.  A term whose coefficient is 0 is not evaluated
+    and comes back as None."""
+    bce, dice, gamma, pw, smooth, _ = check_binary_options(bce, dice, focal_gamma, pos_weight, dice_smooth)
+    if logits.dim() != 4 or logits.shape[1] != 1:
+        raise ValueError(f"BinarySegLoss takes one-channel logits [N, 1, H, W], got {tuple(logits.shape)}")
+    target = binary_target(logits, target)
+    z = logits[:, 0]
+    if target.shape != z.shape:
+        raise ValueError(f"target must be [N, H, W] or [N, 1, H, W] matching the logits {tuple(logits.shape)}, got "
+                         f"{tuple(target.shape)}")
+    valid = target != ignore_index
+    if bool((valid & ((target < 0) | (target > 1))).any()):
+        raise IndexError("Target out of bounds: label(s) outside {0, 1} that are not ignore_index")
+    fg = valid & (target == 1)
+    vf = valid.to(z.dtype)
+    focal = soft = None
+    if bce > 0.0:
+        x = torch.where(fg, z, -z)                                   # pt = sigmoid(x)
+        nlp = F_.softplus(-x)                                        # -log pt = max(-x, 0) + log1p(exp(-|x|))
+        wy = torch.where(fg, torch.full_like(z, pw), torch.ones_like(z))
+        term = wy * nlp
+        if gamma > 0.0:
+            omp = torch.sigmoid(-x)                                  # 1 - pt
+            pos = omp > 0
+            term = term * torch.where(pos, torch.where(pos, omp, torch.ones_like(omp)).pow(gamma),
+                                      torch.zeros_like(omp))         # exactly 0 where 1 - pt is 0
+        # where, not a product with the mask: an ignored pixel's gradient is exactly 0
+        focal = torch.where(valid, term, torch.zeros_like(term)).sum() / vf.sum()
+    if dice > 0.0:
+        s = torch.where(valid, torch.sigmoid(z), torch.zeros_like(z))
+        I = torch.where(fg, s, torch.zeros_like(s)).sum()
+        U = s.sum() + fg.to(z.dtype).sum() + smooth
+        soft = 1.0 - (2.0 * I + smooth) / U
+    loss = None
+    for coef, t in ((bce, focal), (dice, soft)):
+        if t is not None:
+            loss = coef * t if loss is None else loss + coef * t
+    return loss, focal, soft
+
+
 def criterion_loss(logits, target, ignore_index=-100, weight=None, label_smoothing=0.0, reduction="mean", ce=1.0,
-                   dice=0.0, focal_gamma=0.0, dice_smooth=1.0, ohem_thresh=None, ohem_min_kept=None):
+                   dice=0.0, focal_gamma=0.0, dice_smooth=1.0, ohem_thresh=None, ohem_min_kept=None, binary=False,
+                   pos_weight=1.0):
     """What model.forward_loss's keyword arguments describe, on full-resolution logits in torch ops: F.cross_entropy
     for the defaults (nn.CrossEntropyLoss's options), else SegLoss's definition (reduction "mean" only), or
-    OhemCELoss's when ohem_thresh / ohem_min_kept are given."""
+    OhemCELoss's when ohem_thresh / ohem_min_kept are given, or BinarySegLoss's with binary=True (ce is then its bce
+    coefficient)."""
+    if binary:
+        check_binary_combination(weight, label_smoothing, reduction, ohem_thresh, ohem_min_kept)
+        return binary_loss_terms(logits, target, ce, dice, focal_gamma, pos_weight, ignore_index, dice_smooth)[0]
     if ohem_thresh is not None or ohem_min_kept is not None:
         thresh, min_kept = check_ohem_options(ohem_thresh, ohem_min_kept, label_smoothing, reduction, ce, dice,
                                               focal_gamma)
@@ -248,6 +359,53 @@ class SegLoss(nn.Module):
     def extra_repr(self) -> str:
         return (f"ce={self.ce}, dice={self.dice}, focal_gamma={self.focal_gamma}, ignore_index={self.ignore_index}, "
                 f"label_smoothing={self.label_smoothing}, dice_smooth={self.dice_smooth}")
+
+
+class BinarySegLoss(nn.Module):
+    """The sigmoid loss of a one-logit model (lanes, road: MobileNetV2UNet(1), UNet(1), LightUNet):
+    loss = bce * F + dice * Dice, binary cross-entropy with pos_weight and a focal exponent plus the soft Dice of the
+    foreground.
+
+    Logits are [N, 1, H, W]; targets are class-index masks [N, H, W] or [N, 1, H, W] with values in {0, 1,
+    ignore_index}, of an integer or bool dtype (anything but int64 is converted with one torch op; a floating-point
+    target is a TypeError -- soft labels are nn.BCEWithLogitsLoss's business).  Over the valid pixels
+    V = {p : y_p != ignore_index}, with z_p the pixel's logit, t_p = y_p, w_p = pos_weight where t_p = 1 else 1 and
+    pt_p = sigmoid(z_p) where t_p = 1 else sigmoid(-z_p):
+
+        F    = sum_V w_p (1 - pt_p)^gamma (-log pt_p) / |V|
+        I = sum_V sigmoid(z_p) t_p,   S = sum_V sigmoid(z_p),   T = sum_V t_p,   U = S + T + dice_smooth
+        Dice = 1 - (2 I + dice_smooth) / U
+        loss = bce F + dice Dice
+
+    The divisor of F is |V|, not sum w: with gamma = 0 and nothing ignored F is exactly
+    nn.BCEWithLogitsLoss(pos_weight=torch.tensor(pos_weight))(z, t.float()).  A term whose coefficient is 0 is left
+    out (its NaN included); no valid pixel gives NaN (0/0, as aten); (1 - pt)^gamma is exactly 0 where 1 - pt rounds
+    to 0.  The Dice term is over the foreground only and over the whole batch -- per rank under
+    seg_amd.ddp.DataParallel, as SegLoss's.  A label outside {0, 1} that is not ignore_index raises IndexError.
+
+    threshold belongs to validation and inference only: the prediction is 1 iff z > log(threshold / (1 - threshold))
+    (logit_threshold: formed in float64, cast to float).  The comparison is strict, so a tie or a NaN logit is
+    background -- "first maximum wins" for the two-class view [0, z].
+
+    `forward` is this definition in torch ops: the CPU path, the path of any model without `forward_loss`, and the
+    reference the fused kernels (csrc/loss.hip: seg_bce_*) are tested against.  On a seg_amd model on the GPU,
+    seg_amd.train.compute_loss / validate recognise the criterion (fused_loss_options) and never build the
+    full-resolution logits or their gradient."""
+
+    def __init__(self, bce: float = 1.0, dice: float = 0.0, focal_gamma: float = 0.0, pos_weight: float = 1.0,
+                 ignore_index: int = -100, dice_smooth: float = 1.0, threshold: float = 0.5):
+        super().__init__()
+        (self.bce, self.dice, self.focal_gamma, self.pos_weight, self.dice_smooth,
+         self.threshold) = check_binary_options(bce, dice, focal_gamma, pos_weight, dice_smooth, threshold)
+        self.ignore_index = int(ignore_index)
+
+    def forward(self, logits: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+        return binary_loss_terms(logits, target, self.bce, self.dice, self.focal_gamma, self.pos_weight,
+                                 self.ignore_index, self.dice_smooth)[0]
+
+    def extra_repr(self) -> str:
+        return (f"bce={self.bce}, dice={self.dice}, focal_gamma={self.focal_gamma}, pos_weight={self.pos_weight}, "
+                f"ignore_index={self.ignore_index}, dice_smooth={self.dice_smooth}, threshold={self.threshold}")
 
 
 class OhemCELoss(nn.Module):

@@ -42,6 +42,20 @@ def summarize(confusion: torch.Tensor) -> dict:
             "miou": float(iou[valid].mean()) if valid.any() else float("nan")}
 
 
+def binary_summary(confusion: torch.Tensor) -> dict:
+    """{"precision", "recall", "f1"} of class 1 from a [2, 2] confusion matrix (row = label, column = prediction):
+    TP / (TP + FP), TP / (TP + FN) and 2 TP / (2 TP + FP + FN), each NaN where its denominator is 0."""
+    cm = confusion.detach().to("cpu", torch.int64)
+    if tuple(cm.shape) != (2, 2):
+        raise ValueError(f"binary_summary takes a [2, 2] confusion matrix, got {tuple(cm.shape)}")
+    tp, fp, fn = int(cm[1, 1]), int(cm[0, 1]), int(cm[1, 0])
+
+    def ratio(num, den):
+        return num / den if den > 0 else float("nan")
+
+    return {"precision": ratio(tp, tp + fp), "recall": ratio(tp, tp + fn), "f1": ratio(2 * tp, 2 * tp + fp + fn)}
+
+
 def class_weights(counts, scheme: str = "median_frequency", clip: float | None = None) -> torch.Tensor:
     """Class weights for nn.CrossEntropyLoss(weight=...) from pixel counts: a float32 CPU [C] tensor.
 

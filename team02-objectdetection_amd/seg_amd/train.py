@@ -45,8 +45,15 @@ def fused_loss_options(criterion):
     full-resolution tensor.  A seg_amd.SegLoss (again without a forward of its own) adds its four
     scalars: ce, dice, focal_gamma and dice_smooth; a seg_amd.OhemCELoss (the same rule) its two: ohem_thresh and
     ohem_min_kept; a seg_amd.DistillLoss (the same rule) ce, kd, kd_temperature and kd_ignored -- the teacher's
-    logits are compute_loss's to add."""
-    from .losses import DistillLoss, OhemCELoss, SegLoss
+    logits are compute_loss's to add.  A seg_amd.BinarySegLoss (the same rule) gives binary=True with its bce
+    coefficient as ce, and dice, focal_gamma, dice_smooth and pos_weight; its threshold is validation's to add."""
+    from .losses import BinarySegLoss, DistillLoss, OhemCELoss, SegLoss
+    if isinstance(criterion, BinarySegLoss):
+        if type(criterion).forward is not BinarySegLoss.forward:
+            return None
+        return {"ignore_index": criterion.ignore_index, "binary": True, "ce": float(criterion.bce),
+                "dice": float(criterion.dice), "focal_gamma": float(criterion.focal_gamma),
+                "dice_smooth": float(criterion.dice_smooth), "pos_weight": float(criterion.pos_weight)}
     if isinstance(criterion, DistillLoss):
         if type(criterion).forward is not DistillLoss.forward:
             return None
@@ -275,13 +282,23 @@ def validate(model, val_loader, criterion, device, progress: bool = True, epoch:
     probabilities, the matrix from their argmax.  Any fused criterion is then evaluated as its HARD term -- class
     weights, ignore_index, reduction (tta_loss_options): label smoothing, Dice, focal and OHEM terms shape training,
     not an ensemble's report.  Everything else -- the one host wait, the IndexError, the two all-reduces -- is as
-    without it; tta=None runs every line of the path above as it always did."""
-    from .losses import DistillLoss
-    from .metrics import add_confusion, summarize
+    without it; tta=None runs every line of the path above as it always did.
+
+    A seg_amd.BinarySegLoss (one-logit model): the matrix is [2, 2], confusion[label, z > zthr] with
+    zthr = log(threshold / (1 - threshold)) of the criterion's threshold (strict: a tie is background), on the fused
+    branch (seg_bce_upsample_eval) and on the unfused one (logits[:, 0] > zthr, not argmax) alike; the dict
+    additionally holds "precision", "recall" and "f1" of class 1 (seg_amd.metrics.binary_summary).  With tta= it is a
+    ValueError."""
+    from .losses import BinarySegLoss, DistillLoss, binary_target, logit_threshold
+    from .metrics import add_confusion, binary_summary, summarize
     if isinstance(criterion, DistillLoss):
         criterion = criterion.hard()  # validation does not distil: hard-label loss and mIoU, no teacher forward
     core = getattr(model, "module", model)
     ignore_index = getattr(criterion, "ignore_index", -100)
+    binary = isinstance(criterion, BinarySegLoss)
+    if binary and tta is not None:
+        raise ValueError("validate(tta=...) is not defined for a BinarySegLoss: an ensemble of a one-logit model is "
+                         "out of scope")
     if tta is not None:
         from .tta import as_tta
         tta = as_tta(tta)
@@ -290,6 +307,8 @@ def validate(model, val_loader, criterion, device, progress: bool = True, epoch:
         opts = tta_loss_options(criterion)
     else:
         opts = fused_loss_options(criterion) if hasattr(core, "forward_metrics") else None
+        if binary and opts is not None:
+            opts["threshold"] = float(criterion.threshold)
     fused = opts is not None
     it = val_loader
     if progress and tqdm is not None and _is_rank0():
@@ -307,7 +326,7 @@ def validate(model, val_loader, criterion, device, progress: bool = True, epoch:
                     acc = torch.zeros(3, dtype=torch.float64, device=inputs.device)
                 if fused:
                     if confusion is None:
-                        C = _num_classes(core)
+                        C = 2 if binary else _num_classes(core)
                         confusion = torch.zeros((C, C), dtype=torch.int64, device=inputs.device)
                     if tta is not None:
                         loss = model.forward_metrics_tta(inputs, targets, confusion, tta, **opts)
@@ -320,9 +339,13 @@ def validate(model, val_loader, criterion, device, progress: bool = True, epoch:
                     logits = model(inputs)
                     loss = criterion(logits, targets)
                     if confusion is None:
-                        C = logits.shape[1]
+                        C = 2 if binary else logits.shape[1]
                         confusion = torch.zeros((C, C), dtype=torch.int64, device=inputs.device)
-                    add_confusion(confusion, logits.argmax(1), targets, ignore_index)
+                    if binary:  # the criterion's threshold on the one logit, strictly: never argmax
+                        pred = (logits[:, 0] > logit_threshold(criterion.threshold)).to(torch.int64)
+                        add_confusion(confusion, pred, binary_target(logits, targets), ignore_index)
+                    else:
+                        add_confusion(confusion, logits.argmax(1), targets, ignore_index)
                 acc[0] += loss.detach().double()
                 acc[1] += 1
     finally:
@@ -341,6 +364,8 @@ def validate(model, val_loader, criterion, device, progress: bool = True, epoch:
                          "ignore_index (nn.CrossEntropyLoss raises on these)")
     out = {"loss": loss_sum / nb}
     out.update(summarize(host[:-3].reshape(confusion.shape)))
+    if binary:
+        out.update(binary_summary(out["confusion"]))
     return out
 
 

@@ -92,7 +92,7 @@ class _SegModel(nn.Module):
                      label_smoothing: float = 0.0, reduction: str = "mean", *, ce: float = 1.0, dice: float = 0.0,
                      focal_gamma: float = 0.0, dice_smooth: float = 1.0, ohem_thresh=None,
                      ohem_min_kept=None, kd: float = 0.0, kd_temperature: float = 1.0, kd_ignored: bool = True,
-                     teacher_logits=None) -> torch.Tensor:
+                     teacher_logits=None, binary: bool = False, pos_weight: float = 1.0) -> torch.Tensor:
         """nn.CrossEntropyLoss()(self(x), target) (main.py:99, src/train.py:37) fused
         with the final upsample: the full-resolution logits are never stored.
 
@@ -109,15 +109,27 @@ class _SegModel(nn.Module):
         and teacher_logits its teacher's forward_low_logits(x): given kd > 0 (with the tensor), the loss is ce * CE +
         kd * KD against the teacher, whose logits are upsampled inside the loss kernels like the student's (mean
         reduction, class weights, nothing else; GPU tensors only -- on the CPU use the criterion itself).  The
-        defaults are plain cross-entropy, on the code path it always took."""
+        defaults are plain cross-entropy, on the code path it always took.
+
+        binary=True is seg_amd.BinarySegLoss for a one-channel model: ce is then its bce coefficient, dice,
+        focal_gamma and dice_smooth keep their names and pos_weight is its own (seg_bce_* kernels: neither the
+        full-resolution logits nor their gradient are stored).  The target may be [N, 1, H, W] and of any integer or
+        bool dtype.  Class weights, label smoothing, another reduction, OHEM and kd do not combine with it."""
         if x.device.type == "cpu":
             if kd != 0.0 or teacher_logits is not None:
                 raise RuntimeError("forward_loss with kd > 0 runs on the MI355X HIP path only; on CPU tensors "
                                    "evaluate the DistillLoss on the models' logits (seg_amd.train.compute_loss does)")
             from .losses import criterion_loss
+            if binary:
+                return criterion_loss(self(x), target, ignore_index, weight, label_smoothing, reduction, ce, dice,
+                                      focal_gamma, dice_smooth, ohem_thresh, ohem_min_kept, True, pos_weight)
             return criterion_loss(self(x), target, ignore_index, weight, label_smoothing, reduction, ce, dice,
                                   focal_gamma, dice_smooth, ohem_thresh, ohem_min_kept)
         from .engine import run_loss
+        if binary:
+            return run_loss(self, x, target, ignore_index, weight, label_smoothing, reduction, ce, dice, focal_gamma,
+                            dice_smooth, ohem_thresh, ohem_min_kept, kd, kd_temperature, kd_ignored, teacher_logits,
+                            True, pos_weight)
         return run_loss(self, x, target, ignore_index, weight, label_smoothing, reduction, ce, dice, focal_gamma,
                         dice_smooth, ohem_thresh, ohem_min_kept, kd, kd_temperature, kd_ignored, teacher_logits)
 
@@ -131,17 +143,28 @@ class _SegModel(nn.Module):
     def forward_metrics(self, x: torch.Tensor, target: torch.Tensor, confusion: torch.Tensor,
                         ignore_index: int = -100, weight=None, label_smoothing: float = 0.0,
                         reduction: str = "mean", *, ce: float = 1.0, dice: float = 0.0, focal_gamma: float = 0.0,
-                        dice_smooth: float = 1.0, ohem_thresh=None, ohem_min_kept=None) -> torch.Tensor:
+                        dice_smooth: float = 1.0, ohem_thresh=None, ohem_min_kept=None, binary: bool = False,
+                        pos_weight: float = 1.0, threshold: float = 0.5) -> torch.Tensor:
         """Validation step: returns nn.CrossEntropyLoss()(self(x), target) and adds every
         non-ignored pixel to `confusion[label, argmax(self(x))]` (int64 [C, C] on x's device, in
         place), without gradients.  On the MI355X one kernel does both from the low-resolution
         logits: the full-resolution logits are never stored.  weight, label_smoothing, reduction and
         SegLoss's ce, dice, focal_gamma, dice_smooth and OhemCELoss's ohem_thresh, ohem_min_kept (as in forward_loss)
-        change the returned loss only, never the matrix."""
+        change the returned loss only, never the matrix.  binary=True (with pos_weight, as in forward_loss) is
+        seg_amd.BinarySegLoss for a one-channel model: `confusion` is then int64 [2, 2] and the prediction is
+        z > log(threshold / (1 - threshold)), strictly (seg_bce_upsample_eval)."""
         if x.device.type == "cpu":
+            if binary:
+                return _torch_metrics(self, x, target, confusion, ignore_index, weight, label_smoothing, reduction,
+                                      ce, dice, focal_gamma, dice_smooth, ohem_thresh, ohem_min_kept, True,
+                                      pos_weight, threshold)
             return _torch_metrics(self, x, target, confusion, ignore_index, weight, label_smoothing, reduction, ce,
                                   dice, focal_gamma, dice_smooth, ohem_thresh, ohem_min_kept)
         from .engine import run_metrics
+        if binary:
+            return run_metrics(self, x, target, confusion, ignore_index, weight, label_smoothing, reduction, ce,
+                               dice, focal_gamma, dice_smooth, ohem_thresh, ohem_min_kept, True, pos_weight,
+                               threshold)
         return run_metrics(self, x, target, confusion, ignore_index, weight, label_smoothing, reduction, ce, dice,
                            focal_gamma, dice_smooth, ohem_thresh, ohem_min_kept)
 
@@ -174,11 +197,20 @@ class _SegModel(nn.Module):
 
 @torch.no_grad()
 def _torch_metrics(model, x, target, confusion, ignore_index, weight=None, label_smoothing=0.0, reduction="mean",
-                   ce=1.0, dice=0.0, focal_gamma=0.0, dice_smooth=1.0, ohem_thresh=None, ohem_min_kept=None):
-    """forward_metrics in torch ops (CPU tensors): F.cross_entropy raises on an out-of-range label by itself."""
+                   ce=1.0, dice=0.0, focal_gamma=0.0, dice_smooth=1.0, ohem_thresh=None, ohem_min_kept=None,
+                   binary=False, pos_weight=1.0, threshold=0.5):
+    """forward_metrics in torch ops (CPU tensors): F.cross_entropy raises on an out-of-range label by itself.
+    binary: the prediction is logits[:, 0] > zthr and the matrix [2, 2]."""
     from .losses import criterion_loss
     from .metrics import add_confusion
     logits = model(x)
+    if binary:
+        from .losses import binary_target, logit_threshold
+        target = binary_target(logits, target)
+        loss = criterion_loss(logits, target, ignore_index, weight, label_smoothing, reduction, ce, dice,
+                              focal_gamma, dice_smooth, ohem_thresh, ohem_min_kept, True, pos_weight)
+        add_confusion(confusion, (logits[:, 0] > logit_threshold(threshold)).to(torch.int64), target, ignore_index)
+        return loss
     loss = criterion_loss(logits, target, ignore_index, weight, label_smoothing, reduction, ce, dice, focal_gamma,
                           dice_smooth, ohem_thresh, ohem_min_kept)
     add_confusion(confusion, logits.argmax(1), target, ignore_index)
