@@ -994,6 +994,31 @@ int seg_ema_update(const void* tensors, const long* chunks, int nchunks, int chu
  * memory; a second call restores both sides bit for bit. */
 int seg_ema_swap(const void* tensors, const long* chunks, int nchunks, int chunk, hipStream_t stream);
 
+/* ---- SGD with momentum (seg_amd.SGD) over the same chunk map --------------------
+ * The tensor table is a device array of the 56-byte SegAdamWTensor records above,
+ * passed as const void* and filled like this:
+ *   p, g, n            the parameter, its gradient, their element count
+ *   m                  momentum_buffer (NULL, and never read, when momentum == 0)
+ *   v                  unused (NULL)
+ *   step_size, bc2_sqrt, decay   unused
+ *   pad                the seed flag: non-zero on the step that creates this
+ *                      tensor's momentum_buffer, which then receives d itself
+ * torch's foreach SGD (torch/optim/sgd.py::_multi_tensor_sgd) per element, fp32, in
+ * its order, every element read once and written once:
+ *   g = g * *grad_scale                    a product rounded on its own, as seg_adamw_step
+ *   d = g + weight_decay * p               L2 form; weight_decay == 0: d is g bit for bit
+ *   if momentum != 0:
+ *     buf = seed ? d : buf * momentum + one_minus_dampening * d
+ *     d   = nesterov ? d + momentum * buf : buf
+ *   p = p - lr * d
+ * one_minus_dampening is (float)(1 - dampening) formed in double.  skip and
+ * grad_scale: as seg_adamw_step -- when *skip != 0 no parameter and no buffer
+ * changes; .grad is never written.  nchunks < 0 or chunk < 1:
+ * hipErrorInvalidValue; nchunks == 0: success, no launch. */
+int seg_sgd_step(const void* tensors, const long* chunks, int nchunks, int chunk, float lr, float momentum,
+                 float one_minus_dampening, float weight_decay, int nesterov, const float* skip,
+                 const float* grad_scale, hipStream_t stream);
+
 /* ---- launch tape (csrc/tape.hip): a recorded sequence of the launches above,
  *      replayed by one host call per segment -- the engine's training step
  *      (seg_amd/tape.py) without ~600 per-launch ctypes calls.  Not a hipGraph:

@@ -18,7 +18,8 @@
 // gradient (the unused classifier) are simply absent from the table.
 //
 // AdamW and gradient clipping (seg_adamw_step, seg_grad_sumsq, seg_grad_scale) run over the
-// same chunk map with a wider record, SegAdamWTensor; see the second half of this file.
+// same chunk map with a wider record, SegAdamWTensor; see the second half of this file.  SGD with momentum
+// (seg_sgd_step) uses that record too and is the last section.
 #include "common.h"
 
 struct SegAdamTensor {  // 48 bytes, the layout seg_amd/optim.py packs
@@ -301,5 +302,70 @@ SEG_API int seg_ema_swap(const void* tensors, const long* chunks, int nchunks, i
   if (nchunks == 0) return (int)hipSuccess;
   hipLaunchKernelGGL(ema_swap_kernel, dim3(nchunks), dim3(256), 0, stream, (const SegEmaTensor*)tensors, chunks,
                      chunk);
+  SEG_RET_LAST();
+}
+
+// ---- SGD with momentum (seg_amd.SGD) -----------------------------------------------------
+//
+// seg_sgd_step: torch's foreach SGD (torch/optim/sgd.py::_multi_tensor_sgd) over adam_kernel's chunk map, each
+// element read once and written once, fp32, in torch's order:
+//   g = g * (*grad_scale)                  the clip coefficient, as adamw_kernel applies it (mul_rn)
+//   d = g + weight_decay * p               _foreach_add(grads, params, alpha=weight_decay): the L2 form
+//   buf = d                                a tensor's first step: torch clones d, no dampening (the seed flag)
+//   buf = buf * momentum                   _foreach_mul_(bufs, momentum), a rounded product of its own
+//   buf = buf + (1 - dampening) * d        _foreach_add_(bufs, grads, alpha=1 - dampening)
+//   d = nesterov ? d + momentum * buf : buf
+//   p = p - lr * d                         _foreach_add_(params, grads, alpha=-lr)
+// The record is SegAdamWTensor: m is the momentum buffer, v is unused, and the last float (`pad`) is the seed
+// flag -- non-zero on the step that creates the tensor's buffer, which then receives d itself instead of the
+// recurrence (0 * momentum + (1 - dampening) * d is not d when dampening != 0).  The scalars are per parameter
+// group and so kernel arguments.  weight_decay == 0 is a select on the argument, not a multiplication by zero:
+// without decay d is g bit for bit whatever p holds.  momentum == 0 is an instantiation of its own (MOM = false)
+// without the buffer's load and store: the pointer (NULL) is never read.  With MOM the three loads are issued
+// together in front of the arithmetic, as adam_kernel's four are -- on a seeding step the buffer (zeros) is loaded
+// and its value dropped by the select, rather than a branch putting its load behind the other two.  skip:
+// adam_kernel's flag.  Five streams (p, g, buf read; p, buf written) to adam_kernel's seven.
+namespace {
+
+template <bool MOM>
+__global__ __launch_bounds__(256) void sgd_kernel(const SegAdamWTensor* __restrict__ ts,
+                                                  const long* __restrict__ chunks, int chunk, float lr, float momentum,
+                                                  float omd, float wd, int nesterov, const float* __restrict__ skip,
+                                                  const float* __restrict__ grad_scale) {
+  if (skip && *skip != 0.f) return;  // the batch had an out-of-range label: no parameter or buffer changes
+  const float gs = grad_scale ? *grad_scale : 1.f;
+  const long ti = chunks[2 * blockIdx.x], start = chunks[2 * blockIdx.x + 1];
+  const SegAdamWTensor t = ts[ti];
+  const bool seed = t.pad != 0.f;
+  const long end = std::min<long>(t.n, start + chunk);
+  for (long i = start + threadIdx.x; i < end; i += 256) {
+    float d = mul_rn(t.g[i], gs);
+    const float p = t.p[i];
+    float b = MOM ? t.m[i] : 0.f;
+    d = wd != 0.f ? d + wd * p : d;
+    if (MOM) {
+      b = mul_rn(b, momentum);
+      b = b + omd * d;
+      b = seed ? d : b;
+      t.m[i] = b;
+      d = nesterov ? d + momentum * b : b;
+    }
+    t.p[i] = p - lr * d;
+  }
+}
+
+}  // namespace
+
+// tensors: device array of SegAdamWTensor (const void*: include/segamd.h documents how SGD fills the record);
+// chunks / nchunks / chunk / skip / grad_scale as seg_adamw_step.  one_minus_dampening: float(1 - dampening) formed
+// in double.  momentum == 0: no record's m is read.
+SEG_API int seg_sgd_step(const void* tensors, const long* chunks, int nchunks, int chunk, float lr, float momentum,
+                         float one_minus_dampening, float weight_decay, int nesterov, const float* skip,
+                         const float* grad_scale, hipStream_t stream) {
+  if (nchunks < 0 || chunk < 1) return (int)hipErrorInvalidValue;
+  if (nchunks == 0) return (int)hipSuccess;
+  const auto kernel = momentum != 0.f ? sgd_kernel<true> : sgd_kernel<false>;
+  hipLaunchKernelGGL(kernel, dim3(nchunks), dim3(256), 0, stream, (const SegAdamWTensor*)tensors, chunks, chunk, lr,
+                     momentum, one_minus_dampening, weight_decay, nesterov, skip, grad_scale);
   SEG_RET_LAST();
 }

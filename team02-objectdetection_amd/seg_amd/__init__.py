@@ -14,6 +14,10 @@ Public surface (drop-in for the reference's src/unet.py and src/train.py):
                                            both models' final upsamples fused into the loss kernels)
     Adam                                  (main.py:100's optimizer, one-launch HIP step)
     AdamW, decay_groups                   (torch.optim.AdamW as a one-launch HIP step; decayed / undecayed groups)
+    SGD                                   (torch.optim.SGD -- momentum, Nesterov, L2 weight decay -- as a
+                                           one-launch HIP step)
+    PolyLR                                (the poly learning-rate decay with a linear warm-up; train_model(...,
+                                           scheduler=) steps it after every optimizer step)
     grad_norm, clip_grad_norm_            (global L2 gradient norm and clipping on the device)
     EMA                                   (exponential moving average of the weights: one launch per step,
                                            exchanged in place with the live weights for evaluation)
@@ -36,7 +40,8 @@ from .detinit import deterministic_init, synthetic_batch  # noqa: F401
 from .data import CombinedLaneDataset, DistributedWeightedSampler, reference_sample_weights  # noqa: F401
 from .infer import Predictor, preprocess_image  # noqa: F401
 from .overlay import Overlay, overlay_predictions, COLOR_MAP  # noqa: F401
-from .optim import Adam, AdamW, clip_grad_norm_, decay_groups, grad_norm  # noqa: F401
+from .optim import SGD, Adam, AdamW, clip_grad_norm_, decay_groups, grad_norm  # noqa: F401
+from .schedule import PolyLR  # noqa: F401
 from .ema import EMA  # noqa: F401
 from .export import traceable  # noqa: F401
 from .tta import TTA, view_shapes  # noqa: F401
@@ -49,5 +54,6 @@ __all__ = ["MobileNetV2UNet", "UNet", "LightUNet", "double_conv", "inconv", "dow
            "synthetic_batch",
            "CombinedLaneDataset", "DistributedWeightedSampler", "reference_sample_weights",
            "Predictor", "preprocess_image", "Overlay", "overlay_predictions", "COLOR_MAP",
-           "Adam", "AdamW", "clip_grad_norm_", "decay_groups", "grad_norm", "EMA", "TTA", "view_shapes",
+           "Adam", "AdamW", "SGD", "PolyLR", "clip_grad_norm_", "decay_groups", "grad_norm", "EMA", "TTA",
+           "view_shapes",
            "traceable", "freeze", "unfreeze", "frozen_modules"]

@@ -129,6 +129,7 @@ PROTOTYPES = {
     "seg_grad_scale": (_I, [_V, _V, _I, _I, _V, _V]),
     "seg_ema_update": (_I, [_V, _V, _I, _I, _F, _V, _V]),
     "seg_ema_swap": (_I, [_V, _V, _I, _I, _V]),
+    "seg_sgd_step": (_I, [_V, _V, _I, _I, _F, _F, _F, _F, _I, _V, _V, _V]),
     # launch tape (csrc/tape.hip, seg_amd/tape.py)
     "seg_tape_fn_index": (_I, [ctypes.c_char_p]),
     "seg_tape_fn_nargs": (_I, [_I]),

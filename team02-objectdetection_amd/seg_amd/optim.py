@@ -1,4 +1,4 @@
-"""Adam and AdamW with a one-launch HIP step, and global-norm gradient clipping (csrc/adam.hip).
+"""Adam, AdamW and SGD with a one-launch HIP step, and global-norm gradient clipping (csrc/adam.hip).
 
 `Adam` is the drop-in for the reference's `optim.Adam(model.parameters(), lr=1.5e-4)` (main.py:100),
 stepped once per batch by train_model (src/train.py:39): same constructor, same
@@ -16,12 +16,21 @@ lr / betas / eps / weight_decay, lr read at every step (torch.optim.lr_scheduler
 stays refused by `Adam` (its L2 form, added to the gradient, is not implemented), as do amsgrad, maximize,
 capturable and differentiable by both.
 
+`SGD` is the same for `torch.optim.SGD`, the optimizer of the DeepLab / PSPNet / BiSeNet recipes (momentum 0.9,
+often Nesterov, L2 weight decay on the weights, a poly schedule: seg_amd/schedule.py): one seg_sgd_step launch per
+group reads p, g and the momentum buffer and writes p and the buffer, where torch's foreach SGD makes up to five
+multi-tensor passes and a temporary copy of the gradients.  torch's `_multi_tensor_sgd` arithmetic in its order,
+its first step included (the buffer starts as a copy of g + weight_decay * p, without dampening); param_groups and
+state ('momentum_buffer' alone) are torch's.  Refused: maximize, differentiable.
+
 Clipping: `grad_norm` (the global L2 norm, the clip coefficient and a non-finite flag, on the device, no host
 wait), `clip_grad_norm_` (torch.nn.utils.clip_grad_norm_'s contract, L2 only) and `step(grad_scale=...)`, which
 multiplies each gradient element by a device float as the step loads it -- `.grad` is never rewritten.
 `decay_groups` builds the usual two parameter groups (weights decayed, biases and BatchNorm not).
 """
 from __future__ import annotations
+
+import ctypes
 
 import torch
 from torch import nn
@@ -38,14 +47,12 @@ def _chunk_map(sizes, device):
     return torch.tensor(pairs, dtype=torch.int64).reshape(-1, 2).to(device)
 
 
-class _OneLaunchStep:
-    """The host side of Adam and AdamW: argument checks, state, CPU step counters, the tensor table and the launch.
-    _DECOUPLED: the class applies weight decay (AdamW's form); otherwise any weight decay is refused."""
-    _DECOUPLED = False
+class _OneLaunch:
+    """What the one-launch optimizers share: the chunk-map cache, the checks of step()'s device arguments and of a
+    parameter and its gradient, the closure, and the upload of the tensor table."""
 
     def _init_one_launch(self):
         self._chunk_maps = {}
-        self._last_steps = []  # the CPU step counters the last step() advanced (undo_step_count)
 
     def _chunks(self, sizes, device):
         key = (tuple(sizes), device)
@@ -53,6 +60,42 @@ class _OneLaunchStep:
         if cm is None:
             cm = self._chunk_maps[key] = _chunk_map(sizes, device)
         return cm
+
+    @staticmethod
+    def _begin_step(closure, skip_if_nonzero, grad_scale):
+        """Check step()'s two device arguments, then run the closure; returns its loss (None without one)."""
+        for what, t in (("skip_if_nonzero", skip_if_nonzero), ("grad_scale", grad_scale)):
+            if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.numel() >= 1):
+                raise ValueError(f"{what} must be a float32 CUDA tensor")
+        if closure is None:
+            return None
+        with torch.enable_grad():
+            return closure()
+
+    def _check_tensors(self, ps):
+        """The kernels index p and p.grad flatly through raw pointers: anything but dense contiguous fp32 CUDA
+        tensors is refused, before any state is created for the group."""
+        for p in ps:
+            g = p.grad
+            if not (p.is_cuda and p.dtype == torch.float32 and g.dtype == torch.float32 and not g.is_sparse
+                    and p.is_contiguous() and g.is_contiguous()):
+                raise NotImplementedError(
+                    f"seg_amd.{type(self).__name__} needs contiguous fp32 CUDA parameters and gradients")
+
+    @staticmethod
+    def _upload(table, device):
+        """The packed tensor table on `device`: through pinned memory, so that the copy does not wait for the GPU."""
+        return table.pin_memory().to(device, non_blocking=True)
+
+
+class _OneLaunchStep(_OneLaunch):
+    """The host side of Adam and AdamW: argument checks, state, CPU step counters, the tensor table and the launch.
+    _DECOUPLED: the class applies weight decay (AdamW's form); otherwise any weight decay is refused."""
+    _DECOUPLED = False
+
+    def _init_one_launch(self):
+        super()._init_one_launch()
+        self._last_steps = []  # the CPU step counters the last step() advanced (undo_step_count)
 
     @torch.no_grad()
     def step(self, closure=None, *, skip_if_nonzero: torch.Tensor | None = None,
@@ -65,13 +108,7 @@ class _OneLaunchStep:
         grad_scale: a one-element fp32 device tensor (grad_norm(...)[1:2]); every gradient element is multiplied by
         it as it is loaded, bit for bit as if the gradients had been scaled in place first; .grad is not written."""
         name = type(self).__name__
-        loss = None
-        for what, t in (("skip_if_nonzero", skip_if_nonzero), ("grad_scale", grad_scale)):
-            if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.numel() >= 1):
-                raise ValueError(f"{what} must be a float32 CUDA tensor")
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
+        loss = self._begin_step(closure, skip_if_nonzero, grad_scale)
         self._last_steps = []
         wide = self._DECOUPLED or grad_scale is not None  # seg_adamw_step; else seg_adam_step_skip, as ever
         for group in self.param_groups:
@@ -86,11 +123,8 @@ class _OneLaunchStep:
             ps = [p for p in group["params"] if p.grad is not None]
             if not ps:
                 continue
+            self._check_tensors(ps)
             for p in ps:
-                g = p.grad
-                if not (p.is_cuda and p.dtype == torch.float32 and g.dtype == torch.float32 and not g.is_sparse
-                        and p.is_contiguous() and g.is_contiguous()):
-                    raise NotImplementedError(f"seg_amd.{name} needs contiguous fp32 CUDA parameters and gradients")
                 st = self.state[p]
                 if len(st) == 0:
                     st["step"] = torch.tensor(0.0)
@@ -109,7 +143,7 @@ class _OneLaunchStep:
                 tail = (1 - lr * group["weight_decay"] if self._DECOUPLED else 1.0, 0.0)
                 rows = [r + tail for r in rows]
             device = ps[0].device
-            table = (_pack_w(rows) if wide else _pack(rows)).pin_memory().to(device, non_blocking=True)
+            table = self._upload(_pack_w(rows) if wide else _pack(rows), device)
             chunks = self._chunks([p.numel() for p in ps], device)
             skip = skip_if_nonzero.data_ptr() if skip_if_nonzero is not None else None
             stream = torch.cuda.current_stream(device).cuda_stream
@@ -144,6 +178,89 @@ class AdamW(_OneLaunchStep, torch.optim.AdamW):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False, **kw):
         super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, **kw)
         self._init_one_launch()
+
+
+class SGD(_OneLaunch, torch.optim.SGD):
+    """torch.optim.SGD (momentum, dampening, Nesterov, L2 weight decay) with one seg_sgd_step launch per parameter
+    group (module docstring).  The state is torch's: 'momentum_buffer' alone, and only from the first step that had
+    a gradient for the parameter; a buffer that load_state_dict brought continues its recurrence."""
+
+    def __init__(self, params, lr=1e-3, momentum=0, dampening=0, weight_decay=0, nesterov=False, **kw):
+        super().__init__(params, lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay,
+                         nesterov=nesterov, **kw)
+        self._init_one_launch()
+
+    def _init_one_launch(self):
+        super()._init_one_launch()
+        self._last_seeded = []  # the parameters whose momentum_buffer the last step() created (undo_step_count)
+
+    @torch.no_grad()
+    def step(self, closure=None, *, skip_if_nonzero: torch.Tensor | None = None,
+             grad_scale: torch.Tensor | None = None):
+        """One step; skip_if_nonzero and grad_scale as in Adam.step().  A parameter without a momentum_buffer gets
+        one here (zeros at queue time) and the kernel seeds it with d = g + weight_decay * p, torch's first step;
+        undo_step_count() removes the buffers of a step the device skipped.  Every group is checked before the first
+        buffer is created and the first launch queued: a refused step changes nothing."""
+        loss = self._begin_step(closure, skip_if_nonzero, grad_scale)
+        self._last_seeded = []
+        work = []
+        for group in self.param_groups:
+            if group["maximize"] or group.get("differentiable"):
+                raise NotImplementedError("seg_amd.SGD supports maximize and differentiable off only")
+            # the kernel is chosen on the fp32 value (seg_sgd_step's argument): a momentum that underflows there is
+            # no momentum here either, so no buffer is created that no kernel would write
+            momentum = ctypes.c_float(group["momentum"]).value
+            ps = [p for p in group["params"] if p.grad is not None]
+            if not ps:
+                continue
+            self._check_tensors(ps)
+            bufs = None
+            if momentum != 0:  # the buffers that exist (state is a defaultdict: get() creates no entry)
+                bufs = []
+                for p in ps:
+                    st = self.state.get(p)
+                    buf = st.get("momentum_buffer") if st else None
+                    if buf is not None and not (buf.device == p.device and buf.dtype == torch.float32
+                                                and not buf.is_sparse and buf.is_contiguous()
+                                                and buf.shape == p.shape):
+                        raise NotImplementedError("seg_amd.SGD needs contiguous fp32 CUDA momentum buffers")
+                    bufs.append(buf)
+            work.append((group, momentum, ps, bufs))
+        for group, momentum, ps, bufs in work:
+            if bufs is None:
+                rows = [(p.data_ptr(), p.grad.data_ptr(), 0, 0, p.numel(), 0.0, 1.0, 1.0, 0.0) for p in ps]
+            else:
+                rows = []
+                for p, buf in zip(ps, bufs):
+                    seed = 0.0
+                    if buf is None:
+                        buf = torch.zeros_like(p, memory_format=torch.preserve_format)
+                        self.state[p]["momentum_buffer"] = buf
+                        self._last_seeded.append(p)
+                        seed = 1.0
+                    rows.append((p.data_ptr(), p.grad.data_ptr(), buf.data_ptr(), 0, p.numel(), 0.0, 1.0, 1.0, seed))
+            device = ps[0].device
+            table = self._upload(_pack_w(rows), device)
+            chunks = self._chunks([p.numel() for p in ps], device)
+            call("seg_sgd_step", table.data_ptr(), chunks.data_ptr(), chunks.shape[0], _CHUNK, float(group["lr"]),
+                 momentum, 1 - group["dampening"], float(group["weight_decay"]), int(bool(group["nesterov"])),
+                 skip_if_nonzero.data_ptr() if skip_if_nonzero is not None else None,
+                 grad_scale.data_ptr() if grad_scale is not None else None,
+                 torch.cuda.current_stream(device).cuda_stream)
+        return loss
+
+    def undo_step_count(self):
+        """Take back what the last step() changed on the host -- for a step the device skipped (skip_if_nonzero).
+        SGD keeps no step counter; what a skipped step leaves behind is the momentum_buffer entries it created, still
+        zero.  They go, so that state_dict() is what it was and the next real step seeds them as torch's first step
+        does (buf = d, without dampening)."""
+        for p in self._last_seeded:
+            st = self.state.get(p)
+            if st is not None:
+                st.pop("momentum_buffer", None)
+                if not st:
+                    del self.state[p]
+        self._last_seeded = []
 
 
 def _pack(rows):

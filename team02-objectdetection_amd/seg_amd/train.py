@@ -15,8 +15,10 @@ MI355X differences (results are the same):
     kernels (`model.forward_loss`), so the 168 MB of full-resolution logits
     per bs=32 batch are never written;
   * `max_grad_norm` (not in the reference) clips the gradients' global L2 norm before
-    every step; with seg_amd.Adam / seg_amd.AdamW the coefficient stays on the device
-    and is applied inside the step (seg_amd/optim.py);
+    every step; with seg_amd.Adam / seg_amd.AdamW / seg_amd.SGD the coefficient stays on the
+    device and is applied inside the step (seg_amd/optim.py);
+  * `scheduler` (not in the reference) is a learning-rate scheduler stepped after every
+    optimizer step, or once per epoch (seg_amd.PolyLR, torch.optim.lr_scheduler.*);
   * `ema` (not in the reference) keeps an exponential moving average of the weights, one launch
     after every step; validation and `best_checkpoint` then use the averaged model (seg_amd/ema.py);
   * under torch.distributed the gradients are averaged across ranks by
@@ -120,23 +122,24 @@ def _check_labels(model, inputs):
 
 
 def _step_and_loss(model, inputs, optimizer, loss, max_grad_norm=None, ema=None):
-    """optimizer.step() and loss.item() (src/train.py:39-41) with the fused loss's label check.  With seg_amd.Adam
-    or seg_amd.AdamW the step is queued at once and skips itself on the device when the batch (on any rank) had an
-    out-of-range label; the host reads the flag after loss.item(), whose wait covers it, and raises -- no host wait
-    before the step and no extra collective.  Other optimizers: the check runs before the step.
+    """optimizer.step() and loss.item() (src/train.py:39-41) with the fused loss's label check.  With seg_amd.Adam,
+    seg_amd.AdamW or seg_amd.SGD the step is queued at once and skips itself on the device when the batch (on any
+    rank) had an out-of-range label; the host reads the flag after loss.item(), whose wait covers it, and raises --
+    no host wait before the step and no extra collective.  Other optimizers: the check runs
+    before the step.
 
     max_grad_norm: clip the global L2 norm of the gradients of the optimizer's parameters (after
-    finish_gradient_sync they are the averaged ones, the same on every rank: no collective).  The two seg_amd
+    finish_gradient_sync they are the averaged ones, the same on every rank: no collective).  The seg_amd
     optimizers take the coefficient of seg_amd.grad_norm as the step's grad_scale -- nothing waits and .grad stays
     unclipped; any other optimizer gets seg_amd.clip_grad_norm_ in place, after the label check.
 
     ema: a seg_amd.EMA over the same model, updated right after the step.  Behind a step that skips itself on the
     device it gets the same flag (a skipped step is not averaged in, still without a host wait) and its update count
     goes back with the optimizer's before the loop raises; behind a host-side label check it is a plain update()."""
-    from .optim import Adam, AdamW, clip_grad_norm_, grad_norm
+    from .optim import SGD, Adam, AdamW, clip_grad_norm_, grad_norm
     from .engine import label_flag
     flag = label_flag(model) if inputs.is_cuda else None
-    ours = isinstance(optimizer, (Adam, AdamW))
+    ours = isinstance(optimizer, (Adam, AdamW, SGD))
     scale = None
     if max_grad_norm is not None:
         params = [p for group in optimizer.param_groups for p in group["params"]]
@@ -191,13 +194,18 @@ def compute_loss(model, criterion, inputs, targets):
 
 
 def train_one_epoch(model, train_loader, criterion, optimizer, device, epoch: int = 0, epochs: int = 1,
-                    progress: bool = True, augment=None, max_grad_norm: float | None = None, ema=None) -> float:
+                    progress: bool = True, augment=None, max_grad_norm: float | None = None, ema=None,
+                    scheduler=None) -> float:
     """One pass over `train_loader`; returns the mean batch loss (src/train.py:31-44).
 
     max_grad_norm: clip the gradients' global L2 norm to it before every step (_step_and_loss); None: no clipping.
 
     ema: a seg_amd.EMA built over `model`: updated after every optimizer step (one launch, no host wait; a step
     skipped for an out-of-range label is not averaged in).
+
+    scheduler: a learning-rate scheduler over `optimizer` (seg_amd.PolyLR, torch.optim.lr_scheduler.*): its step()
+    is called after every optimizer step.  A batch whose step was skipped for an out-of-range label raises before
+    the scheduler is touched.
 
     augment: optional seg_amd.augment.GpuAugment -- the loader then yields decoded
     uint8 batches (images [N,Hs,Ws,3] RGB, masks [N,Hs,Ws] raw class ids) and the
@@ -226,6 +234,8 @@ def train_one_epoch(model, train_loader, criterion, optimizer, device, epoch: in
         # the update never sees an out-of-range label's NaN gradients, on any rank (nn.CrossEntropyLoss raises in
         # the forward): seg_amd.Adam skips its step on the device, everything else is checked before the step
         lv = _step_and_loss(model, inputs, optimizer, loss, max_grad_norm, ema)
+        if scheduler is not None:
+            scheduler.step()
         train_loss += lv
         nb += 1
         if bar is not None:
@@ -373,7 +383,8 @@ def train_model(model, train_loader, criterion, optimizer, device, epochs=10,
                 checkpoint_pattern: str | None = "Models/obj/obj_MOB_1_epoch_{epoch}.pth", progress: bool = True,
                 augment=None, val_loader=None, best_checkpoint: str | None = None, freeze=None,
                 freeze_epochs: int | None = None, max_grad_norm: float | None = None, ema=None,
-                ema_checkpoint_pattern: str | None = None, val_tta=None):
+                ema_checkpoint_pattern: str | None = None, val_tta=None, scheduler=None,
+                scheduler_interval: str = "step"):
     """Train for `epochs` epochs (src/train.py:6-79).  With `val_loader`, each epoch ends with the
     reference's validation phase (commented out there, src/train.py:46-76): validate(), the
     epoch's result lines, and on an improved validation loss a state_dict at `best_checkpoint`
@@ -393,7 +404,13 @@ def train_model(model, train_loader, criterion, optimizer, device, epochs=10,
     collective) and rank 0 writes the files.  One line at the start says which weights validation uses.
 
     val_tta: validate()'s tta -- the per-epoch validation (and so best_checkpoint's comparison) evaluates the
-    flip / multi-scale ensemble; with `ema` it is the ensemble of the averaged weights."""
+    flip / multi-scale ensemble; with `ema` it is the ensemble of the averaged weights.
+
+    scheduler: a learning-rate scheduler over `optimizer`; scheduler_interval="step" (default) steps it after every
+    optimizer step (train_one_epoch's scheduler -- a per-iteration schedule such as seg_amd.PolyLR), "epoch" once
+    after every epoch's batches, before validation.  Anything else is a ValueError.  None: nothing changes."""
+    if scheduler_interval not in ("step", "epoch"):
+        raise ValueError(f'train_model: scheduler_interval must be "step" or "epoch", got {scheduler_interval!r}')
     from .freeze import freeze as _freeze, unfreeze as _unfreeze
     from .losses import DistillLoss
     if isinstance(criterion, DistillLoss) and _is_rank0():
@@ -423,8 +440,11 @@ def train_model(model, train_loader, criterion, optimizer, device, epochs=10,
         sampler = getattr(train_loader, "sampler", None)
         if hasattr(sampler, "set_epoch"):
             sampler.set_epoch(epoch)  # DistributedWeightedSampler: a new shared draw per epoch
+        kw = {} if scheduler is None or scheduler_interval != "step" else {"scheduler": scheduler}
         avg_train_loss = train_one_epoch(model, train_loader, criterion, optimizer, device, epoch, epochs, progress,
-                                         augment, max_grad_norm, ema)
+                                         augment, max_grad_norm, ema, **kw)
+        if scheduler is not None and scheduler_interval == "epoch":
+            scheduler.step()
         val = None
         if val_loader is not None:  # every rank: validate() all-reduces
             with ema.applied() if ema is not None else contextlib.nullcontext():
